@@ -7,8 +7,13 @@ frame pairs, 1241x376 grey, 2000 features (1000 on the ref frame + 1000 on its l
 path over one batch: --pairs independent pairs per GPU (default 512), inputs (pyramids, features,
 poses) resident in HBM before the timed region.  Data: synthetic street scenes (svo_amd.synth, seeds
 0x5EED0000 + global pair index, SURVEY.md §8(d): every pair its own scene; --distinct D repeats D scenes instead),
-each pair in its own HBM buffers.  The line also times the round 1-5 workload (16 scenes repeated) on the same batch
-(`workload_16_distinct_scenes`).
+each pair in its own HBM buffers.
+
+A plain run sets up, warms up, times --steps steps, writes the last timed step's outputs if --dump-outputs DIR is given
+and prints the line (`value`, `ms_per_step` = the wall time of one timed step).  --full also measures everything else
+the line has keys for, after the timed region: pyramid-build time, single steps, the stage profile, the round 1-5
+workload (16 scenes repeated) on the same batch (`workload_16_distinct_scenes`), end-to-end hand-overs, the other
+median mode, latency, batch scaling, the secondary configs and the CPU baseline with the SE(3) error against it.
 
 Multi-GPU: one process per GPU; pairs are independent, so each rank aligns its own --pairs (weak
 scaling) and there is no data-path collective: the gloo process group is used only for the barrier and
@@ -57,6 +62,15 @@ def parse():
     ap.add_argument("--dump-poses", default="",
                     help="rank 0 writes every rank's per-pair seeds, poses, errors and statuses (gathered in rank order) "
                          "to this .npz (G-invariance tests)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, rank 0 writes what the last timed step computed (what AlignBatch.results "
+                         "returns: every rank's per-pair poses, errors and statuses, in rank order) as DIR/poses.npy, "
+                         "DIR/err.npy and DIR/status.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything else the line can report: pyramid-build timing, single "
+                         "steps, stage profile, the 16-scene workload, end-to-end hand-overs, the other median mode, "
+                         "latency, batch scaling, the secondary configs and the CPU baseline (--no-cpu, --no-secondary "
+                         "and --core-only trim this part); without it those keys are null")
     ap.add_argument("--feature-order", choices=("cell", "shuffled"), default="cell",
                     help="cell: features in the order the reference detector emits them (30-px grid cells row by "
                          "row, src/feature_selection.cpp:103-141); shuffled: random order")
@@ -198,13 +212,15 @@ def main():
         ps.upload(3 * c, arr)
     ctx.synchronize()
     ps.build()  # warm-up (the first launch loads the code objects)
-    pyr_runs = []
-    for _ in range(5):  # median of 5 builds of all 3P frames (the build is idempotent: level 0 stays)
-        ctx.record(2)
-        ps.build()
-        ctx.record(3)
-        pyr_runs.append(ctx.elapsed_ms(2, 3))
-    pyr_ms = float(np.median(pyr_runs))
+    pyr_ms = None
+    if args.full:
+        pyr_runs = []
+        for _ in range(5):  # median of 5 builds of all 3P frames (the build is idempotent: level 0 stays)
+            ctx.record(2)
+            ps.build()
+            ctx.record(3)
+            pyr_runs.append(ctx.elapsed_ms(2, 3))
+        pyr_ms = float(np.median(pyr_runs))
     pyr_bytes = 2 * cam["width"] * cam["height"] + 2 * (level_bytes(cam["width"], cam["height"], L)
                                                        - cam["width"] * cam["height"])
 
@@ -239,16 +255,132 @@ def main():
     # every pair repeats its scene's pose bit for bit (the pairs of one scene run in different sub-batch chains)
     poses_repeat = bool(all(np.array_equal(poses[i], poses[rep[sidx[i]]]) and err[i] == err[rep[sidx[i]]]
                             for i in range(P)))
-    if args.dump_poses:  # every rank's per-pair results, gathered in rank order (host side, outside the timing)
+    if args.dump_poses or args.dump_outputs:  # every rank's per-pair results, gathered in rank order (host side, outside the timing)
         mine = (np.array(seeds, np.int64), poses, err, status)
         parts = [mine]
         if dist:
             parts = [None] * world
             dist.all_gather_object(parts, mine)
-        if rank == 0:
+        if rank == 0 and args.dump_poses:
             np.savez(args.dump_poses, seeds=np.concatenate([q[0] for q in parts]),
                      poses=np.concatenate([q[1] for q in parts]), err=np.concatenate([q[2] for q in parts]),
                      status=np.concatenate([q[3] for q in parts]), world=world)
+        if rank == 0 and args.dump_outputs:  # the last timed step's outputs (a few KB per 100 pairs)
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for k, name in ((1, "poses"), (2, "err"), (3, "status")):
+                np.save(os.path.join(args.dump_outputs, name + ".npy"),
+                        np.concatenate([q[k] for q in parts]).astype(np.float64))
+    step_med = stages = w16 = e2e_s = e2d_s = e2p_ms = e2q_ms = other_line = lat = scaling_lines = None
+    if args.full:
+        (step_med, stages, w16, e2e_s, e2d_s, e2p_ms, e2q_ms, other_line, lat,
+         scaling_lines) = full_measurements(args, ctx, batch, ps, chunks, packed, scenes, sidx, camera, cam, mode, poses)
+    if rank != 0:
+        if dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    value = world * P * args.steps / elapsed
+    b_pair = 3 * level_bytes(cam["width"], cam["height"], L) + nf * 64  # SURVEY.md §8(d)
+    achieved = b_pair * P / (kernel_ms * 1e-3) / 1e9
+    traffic, traffic_src = None, None
+    if args.pmc_json and os.path.exists(args.pmc_json):
+        with open(args.pmc_json) as f:
+            pm = json.load(f)
+        # only a summary measured on this exact workload shape counts
+        if pm.get("pairs") == P and pm.get("features") == nf and pm.get("levels") == L and pm.get("patch") == patch:
+            traffic = pm.get("hbm_bytes_per_launch")
+            traffic_src = os.path.relpath(args.pmc_json, ROOT)
+    dominant = dominant_kernel(args.kernel_stats, P, n_chains(P, mode), b_pair, L) if mode == svo_amd.MEDIAN_REFERENCE else None
+    out = {
+        "metric": METRIC, "value": round(value, 2), "unit": "pairs/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": args.full,
+        "config": {"workload": f"config 2: ImageAlignment::align, {nf} feats ({nf // 2} ref + {nf - nf // 2} lastKF), "
+                               f"patch {patch}, {L}-level pyramid, {cam['width']}x{cam['height']}, {P} pairs/GPU",
+                   "pairs_per_gpu": P, "features": nf, "levels": L, "patch": patch, "distinct_scenes": D,
+                   "feature_order": args.feature_order,
+                   "parallelism": f"pairs sharded over {world} GPU(s), no collective"
+                                  + (" (rehearsal: every rank on device 0)" if shared_gpu else "")},
+        "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
+                     "kernel": f"align chain: {L} levels x (K1 residual [+ pair init at the first level], K2 robust scale, "
+                               f"K3 weights + LM step), {3 * L} launches per chain, {n_chains(P, mode)} concurrent "
+                               f"sub-batch chains",
+                     "kernel_ms": round(kernel_ms, 4), "algorithmic_bytes_per_launch": b_pair * P,
+                     "algorithmic_bytes_per_pair": b_pair, "traffic_source": traffic_src,
+                     "stages_ms": None if stages is None else {k: round(v, 4) for k, v in stages.items()},
+                     "dominant_stage": None if stages is None else max(stages, key=stages.get),
+                     "dominant_kernel": dominant},
+        # the co-limiting roof SURVEY 8(d) names: ~1900 algorithmic fp64 flop per feature and level
+        # (bilinear blends, Jacobian, SE3 / projection, weights, 5 factored accumulators, 21 x 3 expansion)
+        "roofline_fp64_valu": {"achieved": round(1900.0 * nf * L * P / (kernel_ms * 1e-3) / 1e12, 3),
+                               "peak": FP64_VALU_PEAK_TFS, "unit": "TFLOP/s",
+                               "frac": round(1900.0 * nf * L * P / (kernel_ms * 1e-3) / 1e12 / FP64_VALU_PEAK_TFS, 5),
+                               "flop_per_pair": 1900 * nf * L,
+                               "note": "algorithmic flops (SURVEY 8(d) estimate); the issued VALU instructions are "
+                                       "several times more (address, conversion, select): DESIGN 7 SQ counters"},
+        "pyramid_build": None if pyr_ms is None else {
+                          "frames": 3 * P, "ms": round(pyr_ms, 4), "statistic": "median of 5 after a warm-up build",
+                          "frames_per_s": round(3 * P / (pyr_ms * 1e-3), 1),
+                          # algorithmic bytes per frame: read the base image once, write the gradient
+                          # base and levels 1.. of both stacks (SURVEY 8(d) pyramid row)
+                          "algorithmic_bytes_per_frame": pyr_bytes,
+                          "achieved_GBps": round(3 * P * pyr_bytes / (pyr_ms * 1e-3) / 1e9, 1),
+                          "frac_hbm_peak": round(3 * P * pyr_bytes / (pyr_ms * 1e-3) / 8.0e12, 4)},
+        "status_counts": {svo_amd.STATUS_NAMES[int(k)]: int(v) for k, v in zip(*np.unique(status, return_counts=True))},
+        "median_semantics": ("reference: the reference's libstdc++ nth_element post-state (SVO_MEDIAN_REFERENCE)"
+                             if mode == svo_amd.MEDIAN_REFERENCE else "exact order statistics (SVO_MEDIAN_EXACT)"),
+        "poses_repeat_bitexact": poses_repeat,
+        "step_ms_median_of_20": None if step_med is None else round(step_med * 1e3, 4),
+        "other_median_mode": other_line,
+        "end_to_end": None if e2e_s is None else {
+                       "pairs": P, "ms": round(e2e_s * 1e3, 3), "pairs_per_s": round(P / e2e_s, 1),
+                       "note": "from host memory: H2D of 3P base images (pageable), pyramid build, all pairs' "
+                               "features / poses in one svo_align_batch_set_pairs call, alignment, D2H of the results"},
+        # (rounds 1-3 and 5 on: this key is the one-batch-at-a-time median; round 4 alone reported the pipelined
+        # stream under it)
+        "end_to_end_device_images": None if e2d_s is None else {
+                                     "pairs": P, "ms": round(e2d_s * 1e3, 3), "pairs_per_s": round(P / e2d_s, 1),
+                                     "runs": 5, "statistic": "median",
+                                     "note": "SURVEY 8(d): base images already in HBM; one batch at a time: pyramid "
+                                             "build, all pairs' features / poses from host memory in one "
+                                             "svo_align_batch_set_pairs call, alignment, D2H of the results"},
+        "end_to_end_device_images_pipelined": None if e2p_ms is None else {
+            "pairs": P, "ms": round(e2p_ms, 3), "pairs_per_s": round(P / (e2p_ms * 1e-3), 1), "batches": 8,
+            "statistic": "mean over a stream of 8 batches",
+            "note": "the same hand-over for a stream of batches: batch i+1's pyramids build "
+                    "(svo_pyramid_set_build_async, a second PyramidSet) while batch i aligns"},
+        "end_to_end_device_images_two_batches": None if e2q_ms is None else {
+            "pairs": P, "ms": round(e2q_ms, 3), "pairs_per_s": round(P / (e2q_ms * 1e-3), 1), "batches": 8,
+            "statistic": "mean over a stream of 8 batches",
+            "note": "two AlignBatch objects in flight: batch i+1's pyramids build and its features go up (copy stream) "
+                    "while batch i aligns; then batch i's results come back and batch i+1 is queued"},
+        "latency": lat,
+        "batch_scaling": scaling_lines,
+        "workload_16_distinct_scenes": w16,
+        # key meanings across rounds (ADVICE r5): end_to_end_device_images is one batch at a time in rounds 1-3 and 5-6
+        # (round 4 alone reported the pipelined stream under it, now end_to_end_device_images_pipelined); the headline
+        # runs every pair on its own scene from round 6 (16 repeated scenes in rounds 1-5: workload_16_distinct_scenes)
+        "schema": {"round": 6, "end_to_end_device_images": "one batch at a time (rounds 1-3, 5-6)",
+                   "headline_scenes": "one scene per pair (round 6); 16 repeated scenes (rounds 1-5)"},
+    }
+    if args.full and not args.no_secondary:
+        out["secondary"] = secondary(args, ctx, scenes[0], cam, camera)
+    if args.full and not args.no_cpu and world == 1:
+        out.update(cpu_baseline(args, scenes, poses[rep], L, patch, nthreads, mode))
+    print(json.dumps(out), flush=True)
+    if dist:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_measurements(args, ctx, batch, ps, chunks, packed, scenes, sidx, camera, cam, mode, poses):
+    """--full: everything the line reports beside the headline that takes GPU runs of its own, on the headline's batch
+    and pyramids, after the timed region (the batch is left on the headline's pairs).  Returns step_med, stages, w16,
+    e2e_s, e2d_s, e2p_ms, e2q_ms, other_line, lat, scaling_lines."""
+    P, nf, L, patch = args.pairs, args.features, args.levels, args.patch
+    D = P if args.distinct <= 0 else max(1, min(args.distinct, P))
     # per-step time: median of 20 single synchronized steps (host clock), after the timed region
     step_s = []
     for _ in range(20):
@@ -375,102 +507,7 @@ def main():
                       "note": "same pairs; exact order statistics are not the reference's numbers (DESIGN.md)"}
         lat = latency_lines(ctx, scenes, camera, cam, patch, L, nf, mode)
         scaling_lines = batch_scaling(args, ctx, scenes, sidx, camera, cam, patch, L, nf, D, mode, poses)
-    if rank != 0:
-        if dist:
-            dist.barrier()
-            dist.destroy_process_group()
-        return
-
-    value = world * P * args.steps / elapsed
-    b_pair = 3 * level_bytes(cam["width"], cam["height"], L) + nf * 64  # SURVEY.md §8(d)
-    achieved = b_pair * P / (kernel_ms * 1e-3) / 1e9
-    traffic, traffic_src = None, None
-    if args.pmc_json and os.path.exists(args.pmc_json):
-        with open(args.pmc_json) as f:
-            pm = json.load(f)
-        # only a summary measured on this exact workload shape counts
-        if pm.get("pairs") == P and pm.get("features") == nf and pm.get("levels") == L and pm.get("patch") == patch:
-            traffic = pm.get("hbm_bytes_per_launch")
-            traffic_src = os.path.relpath(args.pmc_json, ROOT)
-    dominant = dominant_kernel(args.kernel_stats, P, n_chains(P, mode), b_pair, L) if mode == svo_amd.MEDIAN_REFERENCE else None
-    out = {
-        "metric": METRIC, "value": round(value, 2), "unit": "pairs/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": f"config 2: ImageAlignment::align, {nf} feats ({nf // 2} ref + {nf - nf // 2} lastKF), "
-                               f"patch {patch}, {L}-level pyramid, {cam['width']}x{cam['height']}, {P} pairs/GPU",
-                   "pairs_per_gpu": P, "features": nf, "levels": L, "patch": patch, "distinct_scenes": D,
-                   "feature_order": args.feature_order,
-                   "parallelism": f"pairs sharded over {world} GPU(s), no collective"
-                                  + (" (rehearsal: every rank on device 0)" if shared_gpu else "")},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
-                     "kernel": f"align chain: {L} levels x (K1 residual [+ pair init at the first level], K2 robust scale, "
-                               f"K3 weights + LM step), {3 * L} launches per chain, {n_chains(P, mode)} concurrent "
-                               f"sub-batch chains",
-                     "kernel_ms": round(kernel_ms, 4), "algorithmic_bytes_per_launch": b_pair * P,
-                     "algorithmic_bytes_per_pair": b_pair, "traffic_source": traffic_src,
-                     "stages_ms": {k: round(v, 4) for k, v in stages.items()},
-                     "dominant_stage": max(stages, key=stages.get),
-                     "dominant_kernel": dominant},
-        # the co-limiting roof SURVEY 8(d) names: ~1900 algorithmic fp64 flop per feature and level
-        # (bilinear blends, Jacobian, SE3 / projection, weights, 5 factored accumulators, 21 x 3 expansion)
-        "roofline_fp64_valu": {"achieved": round(1900.0 * nf * L * P / (kernel_ms * 1e-3) / 1e12, 3),
-                               "peak": FP64_VALU_PEAK_TFS, "unit": "TFLOP/s",
-                               "frac": round(1900.0 * nf * L * P / (kernel_ms * 1e-3) / 1e12 / FP64_VALU_PEAK_TFS, 5),
-                               "flop_per_pair": 1900 * nf * L,
-                               "note": "algorithmic flops (SURVEY 8(d) estimate); the issued VALU instructions are "
-                                       "several times more (address, conversion, select): DESIGN 7 SQ counters"},
-        "pyramid_build": {"frames": 3 * P, "ms": round(pyr_ms, 4), "statistic": "median of 5 after a warm-up build",
-                          "frames_per_s": round(3 * P / (pyr_ms * 1e-3), 1),
-                          # algorithmic bytes per frame: read the base image once, write the gradient
-                          # base and levels 1.. of both stacks (SURVEY 8(d) pyramid row)
-                          "algorithmic_bytes_per_frame": pyr_bytes,
-                          "achieved_GBps": round(3 * P * pyr_bytes / (pyr_ms * 1e-3) / 1e9, 1),
-                          "frac_hbm_peak": round(3 * P * pyr_bytes / (pyr_ms * 1e-3) / 8.0e12, 4)},
-        "status_counts": {svo_amd.STATUS_NAMES[int(k)]: int(v) for k, v in zip(*np.unique(status, return_counts=True))},
-        "median_semantics": ("reference: the reference's libstdc++ nth_element post-state (SVO_MEDIAN_REFERENCE)"
-                             if mode == svo_amd.MEDIAN_REFERENCE else "exact order statistics (SVO_MEDIAN_EXACT)"),
-        "poses_repeat_bitexact": poses_repeat,
-        "step_ms_median_of_20": round(step_med * 1e3, 4),
-        "other_median_mode": other_line,
-        "end_to_end": {"pairs": P, "ms": round(e2e_s * 1e3, 3), "pairs_per_s": round(P / e2e_s, 1),
-                       "note": "from host memory: H2D of 3P base images (pageable), pyramid build, all pairs' "
-                               "features / poses in one svo_align_batch_set_pairs call, alignment, D2H of the results"},
-        # (rounds 1-3 and 5 on: this key is the one-batch-at-a-time median; round 4 alone reported the pipelined
-        # stream under it)
-        "end_to_end_device_images": {"pairs": P, "ms": round(e2d_s * 1e3, 3), "pairs_per_s": round(P / e2d_s, 1),
-                                     "runs": 5, "statistic": "median",
-                                     "note": "SURVEY 8(d): base images already in HBM; one batch at a time: pyramid "
-                                             "build, all pairs' features / poses from host memory in one "
-                                             "svo_align_batch_set_pairs call, alignment, D2H of the results"},
-        "end_to_end_device_images_pipelined": None if e2p_ms is None else {
-            "pairs": P, "ms": round(e2p_ms, 3), "pairs_per_s": round(P / (e2p_ms * 1e-3), 1), "batches": 8,
-            "statistic": "mean over a stream of 8 batches",
-            "note": "the same hand-over for a stream of batches: batch i+1's pyramids build "
-                    "(svo_pyramid_set_build_async, a second PyramidSet) while batch i aligns"},
-        "end_to_end_device_images_two_batches": None if e2q_ms is None else {
-            "pairs": P, "ms": round(e2q_ms, 3), "pairs_per_s": round(P / (e2q_ms * 1e-3), 1), "batches": 8,
-            "statistic": "mean over a stream of 8 batches",
-            "note": "two AlignBatch objects in flight: batch i+1's pyramids build and its features go up (copy stream) "
-                    "while batch i aligns; then batch i's results come back and batch i+1 is queued"},
-        "latency": lat,
-        "batch_scaling": scaling_lines,
-        "workload_16_distinct_scenes": w16,
-        # key meanings across rounds (ADVICE r5): end_to_end_device_images is one batch at a time in rounds 1-3 and 5-6
-        # (round 4 alone reported the pipelined stream under it, now end_to_end_device_images_pipelined); the headline
-        # runs every pair on its own scene from round 6 (16 repeated scenes in rounds 1-5: workload_16_distinct_scenes)
-        "schema": {"round": 6, "end_to_end_device_images": "one batch at a time (rounds 1-3, 5-6)",
-                   "headline_scenes": "one scene per pair (round 6); 16 repeated scenes (rounds 1-5)"},
-    }
-    if not args.no_secondary:
-        out["secondary"] = secondary(args, ctx, scenes[0], cam, camera)
-    if not args.no_cpu and world == 1:
-        out.update(cpu_baseline(args, scenes, poses[rep], L, patch, nthreads, mode))
-    print(json.dumps(out), flush=True)
-    if dist:
-        dist.barrier()
-        dist.destroy_process_group()
+    return step_med, stages, w16, e2e_s, e2d_s, e2p_ms, e2q_ms, other_line, lat, scaling_lines
 
 
 def dominant_kernel(path, P, chains, b_pair, L):

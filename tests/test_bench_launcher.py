@@ -8,9 +8,10 @@ import subprocess
 import sys
 
 import numpy as np
+import pytest
 
 import svo_amd.synth as synth
-from common import oracle_align
+from common import canon, oracle_align
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARGS = ["--pairs", "2", "--features", "120", "--levels", "3", "--steps", "1", "--warmup", "0", "--cpu-rehearsal"]
@@ -62,3 +63,34 @@ def test_bench_chain_count_follows_the_library():
     assert bench.n_chains(const["kSplitsRefvMin"] - 1, ref) == const["kSplits"]
     assert bench.n_chains(const["kSplitsRefvMin"], ref) == const["kSplitsRefv"]
     assert bench.n_chains(const["kSplitsRefvMin"], exact) == const["kSplits"]
+
+
+@pytest.mark.gpu
+def test_gpu_plain_run_dumps_the_timed_outputs(tmp_path):
+    """A plain run (no --full) times --steps steps, reports ms_per_step, leaves every --full figure null, and
+    --dump-outputs holds what the last timed step computed: the arrays AlignBatch.results returns, as float64 .npy
+    files, pair 0's pose the oracle's."""
+    d = tmp_path / "out"
+    e = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--pairs", "8", "--features", "300",
+                        "--levels", "3", "--steps", "2", "--warmup", "1", "--dump-outputs", str(d),
+                        "--dump-poses", str(tmp_path / "p.npz")], capture_output=True, text=True, timeout=300, env=e,
+                       cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["unit"] == "pairs/s" and out["dtype"] == "f64"
+    assert abs(out["value"] - 8 / (out["ms_per_step"] * 1e-3)) <= 1e-3 * out["value"]
+    assert out["full"] is False and "secondary" not in out and "cpu_baseline" not in out
+    for k in ("latency", "batch_scaling", "other_median_mode", "end_to_end", "pyramid_build", "step_ms_median_of_20"):
+        assert out[k] is None, k
+    ref = np.load(tmp_path / "p.npz")
+    got = {n: np.load(d / (n + ".npy")) for n in ("poses", "err", "status")}
+    assert sorted(os.listdir(d)) == ["err.npy", "poses.npy", "status.npy"]
+    assert all(a.dtype == np.float64 for a in got.values()) and got["poses"].shape == (8, 7)
+    for n in got:
+        assert np.array_equal(got[n], ref[n].astype(np.float64)), n
+    s = synth.make_pair(seed=synth.SEED_BASE, n_features=300, patch_size=5, cell_order=30)
+    pose, err, st, _ = oracle_align(s, 5, 0, 2, mode=0, trace=False)
+    assert got["status"][0] == st and np.abs(canon(got["poses"][0]) - canon(pose)).max() <= 1e-9

@@ -358,6 +358,48 @@ int svo_pose_optimize(svo_ctx* ctx, int32_t n_frames, const int32_t* feat_off, c
                       const double* point, const uint8_t* has_point, uint8_t* vis_inout, double* poses_inout,
                       double* err, int32_t* status);
 
+/* ---------------------------------------------------------------- two-view map initialisation
+ * Replaces algorithm::triangulate3DWorldPoints(refFrame, curFrame, pointsWorld) (src/algorithm.cpp:553-566 with
+ * triangulatePointDLT :655-680) for n_pairs independent frame pairs: pair p owns matches feat_off[p] ..
+ * feat_off[p+1]-1 (feat_off[0] = 0, ascending); match k is ref_px[2k..] in the frame posed ref_poses[7p..] and
+ * cur_px[2k..] in the frame posed cur_poses[7p..].  Per match the 4x3 system of both projection matrices
+ * K * pose.matrix3x4(), its normal equations and Eigen's LDLT on the 3x3.  points_world: n x 3.  Synchronous. */
+int svo_triangulate_dlt(svo_ctx* ctx, const svo_camera* cam, int32_t n_pairs, const int32_t* feat_off,
+                        const double* ref_poses, const double* cur_poses, const double* ref_px, const double* cur_px,
+                        double* points_world);
+
+/* Replaces the map initialisation of System::processSecondFrame from the essential matrix on
+ * (src/system.cpp:144-223) for n_pairs independent frame pairs, matches laid out as for svo_triangulate_dlt:
+ * F = invK^T E invK (:144), algorithm::sampsonCorrection (src/algorithm.cpp:173-237), recoverPose with
+ * decomposeEssentialMatrix (:241-333), the triangulation against the recovered pose, computeMedian (:813-832) of
+ * the current-camera norms, the rescaling to map_scale (m_initMapScaleFactor, :179-190) and the validity test with
+ * halfPatchSize = ceil(cell_size / 2) (:196-202).  It ends where twoViewBA would be called (:229).
+ *   E            n_pairs x 9, row-major (the caller's findEssentialMat result)
+ *   ref_poses    n_pairs x 7
+ *   ref_px, cur_px  in: the matched pixels; out: Sampson-corrected (also for a pair that fails afterwards)
+ *   F            n_pairs x 9, row-major
+ *   counts       n_pairs x 4: matches with z > 0 in both cameras under (R1,t) (R1,-t) (R2,t) (R2,-t), each
+ *                hypothesis posed as poses[i] * ref_pose (:297).  Which of the two rotations an SVD calls R1 and
+ *                which sign it gives t is a convention of the SVD; the set of four is not.
+ *   winner       n_pairs: the first hypothesis with the strictly largest count (:318); -1 when every count is 0:
+ *                recoverPose fails, the rest of that pair's outputs are median_depth NaN, n_valid 0, valid 0,
+ *                survivor -1, points and depths 0, and its cur_poses row is left as the caller had it
+ *   cur_poses    n_pairs x 7: poses[winner] alone, without the reference frame's pose (:329), its translation
+ *                rewritten as -R_cur (C_ref + s (C_cur - C_ref)) with s = map_scale / median_depth (:184-186)
+ *   median_depth n_pairs: the median before scaling; for an even count (vec[mid-1] + vec[mid]) / 2 with vec[mid-1]
+ *                as libstdc++'s std::nth_element leaves it
+ *   n_valid      n_pairs: matches with isInFrame(ref px, h) && isInFrame(cur px, h) && z_cur > 0
+ *   points_world n x 3: the rescaled points (of every match, valid or not)
+ *   valid        n: that test per match
+ *   survivor     n: per pair, at feat_off[p], the indices within the pair of its valid matches in match order
+ *                (the features remove_if keeps, :217-223), then -1
+ *   depth        n, may be NULL: the current-camera norms median_depth was taken from
+ * Synchronous. */
+int svo_two_view_init(svo_ctx* ctx, const svo_camera* cam, int32_t n_pairs, const int32_t* feat_off, const double* E,
+                      const double* ref_poses, double map_scale, int32_t cell_size, double* ref_px, double* cur_px,
+                      double* F, int32_t* counts, int32_t* winner, double* cur_poses, double* median_depth,
+                      int32_t* n_valid, double* points_world, uint8_t* valid, int32_t* survivor, double* depth);
+
 #ifdef __cplusplus
 }
 #endif

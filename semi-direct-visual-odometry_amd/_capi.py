@@ -101,6 +101,11 @@ _SIGNATURES = [
     ("svo_format_kitti_pose", c_int32, [c_void_p, ctypes.c_char_p, c_int32]),
     ("svo_pose_optimize", c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p]),
+    ("svo_triangulate_dlt", c_int32, [c_void_p, ctypes.POINTER(SvoCamera), c_int32, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p]),
+    ("svo_two_view_init", c_int32, [c_void_p, ctypes.POINTER(SvoCamera), c_int32, c_void_p, c_void_p, c_void_p,
+                                    c_double, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 ]
 
 EXPORTED = [s[0] for s in _SIGNATURES]

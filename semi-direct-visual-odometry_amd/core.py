@@ -1147,3 +1147,107 @@ class BundleAdjustment:
         frame.abs_pose = poses[0].copy()
         self.last_status = int(st[0])
         return float(err[0])
+
+
+# ---------------------------------------------------------------- two-view map initialisation
+def _c_f64(a, shape, name):
+    if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.shape == shape):
+        raise ValueError(f"{name} must be a C-contiguous float64 array of shape {shape} (it is updated in place)")
+    return a
+
+
+def triangulate_batch(camera, feat_off, ref_poses, cur_poses, ref_px, cur_px, ctx=None):
+    """svo_triangulate_dlt (algorithm::triangulate3DWorldPoints, src/algorithm.cpp:553-566) over arrays: pair p
+    owns matches feat_off[p]:feat_off[p+1], posed ref_poses[p] / cur_poses[p].  Returns points_world (n, 3)."""
+    ctx = ctx or default_context()
+    feat_off = np.ascontiguousarray(feat_off, np.int32)
+    P = len(feat_off) - 1
+    n = int(feat_off[-1])
+    ref_poses = np.ascontiguousarray(ref_poses, np.float64).reshape(P, 7)
+    cur_poses = np.ascontiguousarray(cur_poses, np.float64).reshape(P, 7)
+    ref_px = np.ascontiguousarray(ref_px, np.float64).reshape(n, 2)
+    cur_px = np.ascontiguousarray(cur_px, np.float64).reshape(n, 2)
+    out = np.zeros((n, 3))
+    cam = camera.as_c()
+    check(lib().svo_triangulate_dlt(ctx.handle, ctypes.byref(cam), P, ptr(feat_off), ptr(ref_poses), ptr(cur_poses),
+                                    ptr(ref_px), ptr(cur_px), ptr(out)))
+    return out
+
+
+class TwoViewResult:
+    """Outputs of two_view_init_batch (include/svo_c.h svo_two_view_init): F (P, 3, 3), counts (P, 4), winner (P,),
+    cur_poses (P, 7; NaN rows for failed pairs), median_depth (P,), n_valid (P,), points_world (n, 3), valid (n,),
+    survivor (n,), depth (n,)."""
+    __slots__ = ("F", "counts", "winner", "cur_poses", "median_depth", "n_valid", "points_world", "valid", "survivor",
+                 "depth")
+
+
+def two_view_init_batch(camera, feat_off, E, ref_poses, ref_px, cur_px, map_scale, cell_size, ctx=None):
+    """svo_two_view_init over arrays (System::processSecondFrame from the essential matrix on,
+    src/system.cpp:144-223).  ref_px / cur_px ((n, 2) float64, C-contiguous) are Sampson-corrected in place."""
+    ctx = ctx or default_context()
+    feat_off = np.ascontiguousarray(feat_off, np.int32)
+    P = len(feat_off) - 1
+    n = int(feat_off[-1])
+    E = np.ascontiguousarray(E, np.float64).reshape(P, 9)
+    ref_poses = np.ascontiguousarray(ref_poses, np.float64).reshape(P, 7)
+    _c_f64(ref_px, (n, 2), "ref_px")
+    _c_f64(cur_px, (n, 2), "cur_px")
+    r = TwoViewResult()
+    r.F = np.zeros((P, 3, 3))
+    r.counts = np.zeros((P, 4), np.int32)
+    r.winner = np.zeros(P, np.int32)
+    r.cur_poses = np.full((P, 7), np.nan)  # the call leaves a failed pair's row alone
+    r.median_depth = np.zeros(P)
+    r.n_valid = np.zeros(P, np.int32)
+    r.points_world = np.zeros((n, 3))
+    r.valid = np.zeros(n, np.uint8)
+    r.survivor = np.zeros(n, np.int32)
+    r.depth = np.zeros(n)
+    cam = camera.as_c()
+    check(lib().svo_two_view_init(ctx.handle, ctypes.byref(cam), P, ptr(feat_off), ptr(E), ptr(ref_poses),
+                                  float(map_scale), int(cell_size), ptr(ref_px), ptr(cur_px), ptr(r.F), ptr(r.counts),
+                                  ptr(r.winner), ptr(r.cur_poses), ptr(r.median_depth), ptr(r.n_valid),
+                                  ptr(r.points_world), ptr(r.valid), ptr(r.survivor), ptr(r.depth)))
+    return r
+
+
+def _set_pixels(frame, px):
+    """Feature.pixel_position of every feature of `frame` <- the rows of px, with one bump of the frame's feature
+    version (the rows of one frozen copy, as Feature._many lays them out)."""
+    rows = _frozen(px)
+    for f, row in zip(frame.features, rows):
+        f._px = row
+    frame._feat_ver[0] += 1
+
+
+def two_view_initialize(ref_frame, cur_frame, E, map_scale, cell_size, ctx=None):
+    """What System::processSecondFrame does to the two frames between computeEssentialMatrix and twoViewBA
+    (src/system.cpp:144-223): Sampson-corrected pixel positions in both frames, cur_frame.abs_pose, one Point per
+    valid match linked both ways, and the features without a point erased from both frames (order kept).
+    Feature i of ref_frame matches feature i of cur_frame.  Returns (ok, median depth before scaling, number of
+    points); ok False when recoverPose fails: the pixels stay corrected, nothing else changes (:152-156)."""
+    n = ref_frame.number_observation()
+    if cur_frame.number_observation() != n:
+        raise ValueError("ref_frame and cur_frame must hold the same number of (matched) features")
+    # (the gathers also form every bearing from the uncorrected pixel, as the reference's Feature constructor did)
+    ref_px = np.array(ref_frame.feature_arrays()[0], np.float64).reshape(n, 2)
+    cur_px = np.array(cur_frame.feature_arrays()[0], np.float64).reshape(n, 2)
+    r = two_view_init_batch(ref_frame.camera, [0, n], np.asarray(E, np.float64).reshape(1, 9),
+                            np.asarray(ref_frame.abs_pose, np.float64).reshape(1, 7), ref_px, cur_px, map_scale,
+                            cell_size, ctx)
+    _set_pixels(ref_frame, ref_px)  # sampsonCorrection (src/algorithm.cpp:233-234)
+    _set_pixels(cur_frame, cur_px)
+    if r.winner[0] < 0:
+        return False, float("nan"), 0
+    cur_frame.abs_pose = r.cur_poses[0].copy()
+    for i in r.survivor[:int(r.n_valid[0])]:  # (:201-209)
+        point = Point(r.points_world[i])
+        fr, fc = ref_frame.features[i], cur_frame.features[i]
+        fr.set_point(point)
+        fc.set_point(point)
+        point.add_feature(fr)
+        point.add_feature(fc)
+    for fr in (ref_frame, cur_frame):  # remove_if(m_point == nullptr) (:217-223)
+        fr.features = [f for f in fr.features if f.point is not None]
+    return True, float(r.median_depth[0]), int(r.n_valid[0])

@@ -1593,4 +1593,166 @@ int svo_pose_optimize(svo_ctx* c, int32_t n_frames, const int32_t* feat_off, con
     return SVO_OK;
 }
 
+// ------------------------------------------------------------------ two-view map initialisation
+// sizes first, then pointers: the checks that need no device run before the context is looked at
+static int two_view_check(const char* fn, int32_t n_pairs, const int32_t* feat_off, int64_t* n_out) {
+    if (n_pairs < 0) return fail(SVO_ERR_ARG, "%s: n_pairs < 0", fn);
+    if (!feat_off) return fail(SVO_ERR_ARG, "%s: null argument (feat_off)", fn);
+    if (feat_off[0] != 0) return fail(SVO_ERR_ARG, "%s: feat_off[0] must be 0", fn);
+    for (int32_t p = 0; p < n_pairs; ++p)
+        if (feat_off[p + 1] < feat_off[p]) return fail(SVO_ERR_ARG, "%s: feat_off not ascending at pair %d", fn, p);
+    if (feat_off[n_pairs] >= ((int32_t)1 << 28)) return fail(SVO_ERR_ARG, "%s: too many matches", fn);
+    *n_out = feat_off[n_pairs];
+    return SVO_OK;
+}
+
+namespace {
+struct Carve {  // 8-byte aligned pieces of one device block
+    size_t total = 0;
+    size_t take(size_t bytes) {
+        const size_t o = total;
+        total += (bytes + 7) / 8 * 8;
+        return o;
+    }
+};
+}  // namespace
+
+int svo_triangulate_dlt(svo_ctx* c, const svo_camera* cam, int32_t n_pairs, const int32_t* feat_off,
+                        const double* ref_poses, const double* cur_poses, const double* ref_px, const double* cur_px,
+                        double* points_world) {
+    int64_t n = 0;
+    if (int r = two_view_check("svo_triangulate_dlt", n_pairs, feat_off, &n)) return r;
+    if (!c || !cam || (n_pairs > 0 && (!ref_poses || !cur_poses)) || (n > 0 && (!ref_px || !cur_px || !points_world)))
+        return fail(SVO_ERR_ARG, "svo_triangulate_dlt: null argument");
+    if (n_pairs == 0 || n == 0) return SVO_OK;
+    SVO_HIP(hipSetDevice(c->device));
+    hipStream_t s = ctx_stream(c);
+    const size_t P = (size_t)n_pairs, N = (size_t)n;
+    Carve cv;
+    const size_t o_off = cv.take((P + 1) * 4), o_rp = cv.take(P * 56), o_cp = cv.take(P * 56), o_rpx = cv.take(N * 16),
+                 o_cpx = cv.take(N * 16), o_pw = cv.take(N * 24);
+    void* base = nullptr;
+    hipError_t e = ctx_scratch(c, cv.total, &base);
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, "two-view scratch: %s", hipGetErrorString(e));
+    char* db = static_cast<char*>(base);
+    struct Piece { size_t off; const void* src; size_t bytes; };
+    const Piece in[] = {{o_off, feat_off, (P + 1) * 4}, {o_rp, ref_poses, P * 56}, {o_cp, cur_poses, P * 56},
+                        {o_rpx, ref_px, N * 16}, {o_cpx, cur_px, N * 16}};
+    for (const Piece& pc : in)
+        if (e == hipSuccess) e = stage_copy(c, db + pc.off, pc.src, pc.bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) {
+        svo::TwoViewArgs a{};
+        a.feat_off = reinterpret_cast<int32_t*>(db + o_off);
+        a.ref_poses = reinterpret_cast<double*>(db + o_rp);
+        a.cur_pose = reinterpret_cast<double*>(db + o_cp);
+        a.ref_px = reinterpret_cast<double*>(db + o_rpx);
+        a.cur_px = reinterpret_cast<double*>(db + o_cpx);
+        a.points_world = reinterpret_cast<double*>(db + o_pw);
+        a.fx = cam->fx; a.fy = cam->fy; a.cx = cam->cx; a.cy = cam->cy;
+        a.width = cam->width; a.height = cam->height; a.n_pairs = n_pairs;
+        svo::launch_triangulate_dlt(a, s);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = stage_copy(c, points_world, db + o_pw, N * 24, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, "svo_triangulate_dlt: %s", hipGetErrorString(e));
+    return SVO_OK;
+}
+
+int svo_two_view_init(svo_ctx* c, const svo_camera* cam, int32_t n_pairs, const int32_t* feat_off, const double* E,
+                      const double* ref_poses, double map_scale, int32_t cell_size, double* ref_px, double* cur_px,
+                      double* F, int32_t* counts, int32_t* winner, double* cur_poses, double* median_depth,
+                      int32_t* n_valid, double* points_world, uint8_t* valid, int32_t* survivor, double* depth) {
+    int64_t n = 0;
+    if (int r = two_view_check("svo_two_view_init", n_pairs, feat_off, &n)) return r;
+    if (cell_size < 1) return fail(SVO_ERR_ARG, "svo_two_view_init: cell_size < 1");
+    if (!(map_scale > 0.0) || !std::isfinite(map_scale))
+        return fail(SVO_ERR_ARG, "svo_two_view_init: map_scale must be positive and finite");
+    if (!c || !cam ||
+        (n_pairs > 0 && (!E || !ref_poses || !F || !counts || !winner || !cur_poses || !median_depth || !n_valid)) ||
+        (n > 0 && (!ref_px || !cur_px || !points_world || !valid || !survivor)))
+        return fail(SVO_ERR_ARG, "svo_two_view_init: null argument");
+    if (n_pairs == 0) return SVO_OK;
+    const size_t P = (size_t)n_pairs, N = (size_t)n;
+    // host: F and the four poses of every pair
+    std::vector<double> hyp(28 * P), scale(P, 0.0), dep(N), pose(7 * P);
+    for (size_t p = 0; p < P; ++p) {
+        svo::two_view_fundamental(*cam, E + 9 * p, F + 9 * p);
+        svo::two_view_hypotheses(E + 9 * p, hyp.data() + 28 * p);
+    }
+    SVO_HIP(hipSetDevice(c->device));
+    hipStream_t s = ctx_stream(c);
+    Carve cv;
+    const size_t o_off = cv.take((P + 1) * 4), o_F = cv.take(P * 72), o_rp = cv.take(P * 56), o_hyp = cv.take(P * 224),
+                 o_rpx = cv.take(N * 16), o_cpx = cv.take(N * 16), o_cnt = cv.take(P * 16), o_win = cv.take(P * 4),
+                 o_cp = cv.take(P * 56), o_pw = cv.take(N * 24), o_pc = cv.take(N * 24), o_dep = cv.take(N * 8),
+                 o_sc = cv.take(P * 8), o_val = cv.take(N), o_sur = cv.take(N * 4), o_nv = cv.take(P * 4);
+    void* base = nullptr;
+    hipError_t e = ctx_scratch(c, cv.total, &base);
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, "two-view scratch: %s", hipGetErrorString(e));
+    char* db = static_cast<char*>(base);
+    struct Piece { size_t off; const void* src; size_t bytes; };
+    const Piece in[] = {{o_off, feat_off, (P + 1) * 4}, {o_F, F, P * 72}, {o_rp, ref_poses, P * 56},
+                        {o_hyp, hyp.data(), P * 224}, {o_rpx, ref_px, N * 16}, {o_cpx, cur_px, N * 16}};
+    for (const Piece& pc : in)
+        if (e == hipSuccess) e = stage_copy(c, db + pc.off, pc.src, pc.bytes, hipMemcpyHostToDevice, s);
+    svo::TwoViewArgs a{};
+    a.feat_off = reinterpret_cast<int32_t*>(db + o_off);
+    a.F = reinterpret_cast<double*>(db + o_F);
+    a.ref_poses = reinterpret_cast<double*>(db + o_rp);
+    a.hyp = reinterpret_cast<double*>(db + o_hyp);
+    a.ref_px = reinterpret_cast<double*>(db + o_rpx);
+    a.cur_px = reinterpret_cast<double*>(db + o_cpx);
+    a.counts = reinterpret_cast<int32_t*>(db + o_cnt);
+    a.winner = reinterpret_cast<int32_t*>(db + o_win);
+    a.cur_pose = reinterpret_cast<double*>(db + o_cp);
+    a.points_world = reinterpret_cast<double*>(db + o_pw);
+    a.points_cur = reinterpret_cast<double*>(db + o_pc);
+    a.depth = reinterpret_cast<double*>(db + o_dep);
+    a.scale = reinterpret_cast<double*>(db + o_sc);
+    a.valid = reinterpret_cast<uint8_t*>(db + o_val);
+    a.survivor = reinterpret_cast<int32_t*>(db + o_sur);
+    a.n_valid = reinterpret_cast<int32_t*>(db + o_nv);
+    a.fx = cam->fx; a.fy = cam->fy; a.cx = cam->cx; a.cy = cam->cy;
+    a.half_patch = std::ceil(static_cast<double>(cell_size) / 2.0);  // halfPatchSize (src/system.cpp:196)
+    a.width = cam->width; a.height = cam->height; a.n_pairs = n_pairs;
+    if (e == hipSuccess) {
+        svo::launch_two_view_vote(a, s);
+        e = hipGetLastError();
+    }
+    struct Out { size_t off; void* dst; size_t bytes; };
+    const Out mid[] = {{o_cnt, counts, P * 16}, {o_win, winner, P * 4}, {o_cp, pose.data(), P * 56},
+                       {o_dep, dep.data(), N * 8}};
+    for (const Out& o : mid)
+        if (e == hipSuccess) e = stage_copy(c, o.dst, db + o.off, o.bytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, "svo_two_view_init: %s", hipGetErrorString(e));
+    // host: median depth, scale = map_scale / median and the rescaled pose of every pair that has a winner
+    // (src/system.cpp:172-186); a failed pair keeps the caller's cur_poses row
+    for (size_t p = 0; p < P; ++p) {
+        median_depth[p] = std::numeric_limits<double>::quiet_NaN();
+        if (winner[p] < 0) continue;
+        median_depth[p] = svo::two_view_median(dep.data() + feat_off[p], feat_off[p + 1] - feat_off[p]);
+        scale[p] = map_scale / median_depth[p];
+        svo::two_view_rescale_pose(ref_poses + 7 * p, scale[p], pose.data() + 7 * p);
+        std::memcpy(cur_poses + 7 * p, pose.data() + 7 * p, 56);
+    }
+    e = stage_copy(c, db + o_sc, scale.data(), P * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = stage_copy(c, db + o_cp, pose.data(), P * 56, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) {
+        svo::launch_two_view_finish(a, s);
+        e = hipGetLastError();
+    }
+    const Out out[] = {{o_rpx, ref_px, N * 16}, {o_cpx, cur_px, N * 16}, {o_pw, points_world, N * 24},
+                       {o_val, valid, N}, {o_sur, survivor, N * 4}, {o_nv, n_valid, P * 4}};
+    for (const Out& o : out)
+        if (e == hipSuccess) e = stage_copy(c, o.dst, db + o.off, o.bytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, "svo_two_view_init: %s", hipGetErrorString(e));
+    if (depth)
+        for (size_t p = 0; p < P; ++p)  // a failed pair has no depths
+            for (int64_t k = feat_off[p]; k < feat_off[p + 1]; ++k) depth[k] = winner[p] < 0 ? 0.0 : dep[k];
+    return SVO_OK;
+}
+
 }  // extern "C"

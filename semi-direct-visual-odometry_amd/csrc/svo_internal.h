@@ -193,6 +193,36 @@ struct PoseBAArgs {  // BundleAdjustment::optimizePose over a batch of frames (p
 };
 void launch_pose_ba(const PoseBAArgs& a, hipStream_t s);
 
+struct TwoViewArgs {  // two-view map initialisation over a batch of frame pairs (two_view.hip)
+    const int32_t* feat_off;   // [n_pairs + 1] match range of each pair
+    const double* F;           // [n_pairs][9] fundamental matrix, row-major
+    const double* ref_poses;   // [n_pairs][7]
+    const double* hyp;         // [n_pairs][4][7] the poses of recoverPose: (R1,t) (R1,-t) (R2,t) (R2,-t)
+    double* ref_px;            // [n][2] in: matched pixels; out: Sampson-corrected
+    double* cur_px;            // [n][2]
+    int32_t* counts;           // [n_pairs][4] matches in front of both cameras per hypothesis
+    int32_t* winner;           // [n_pairs] -1: no hypothesis with a positive count
+    double* cur_pose;          // [n_pairs][7] vote: poses[winner]; the host then writes the rescaled pose here
+                               // (triangulate_dlt_kernel: the caller's cur poses)
+    double* points_world;      // [n][3]
+    double* points_cur;        // [n][3] scratch: the point in the current camera before scaling
+    double* depth;             // [n] its norm
+    const double* scale;       // [n_pairs] map_scale / median (finish)
+    uint8_t* valid;            // [n]
+    int32_t* survivor;         // [n] per pair: the indices (within the pair) of its valid matches in order, then -1
+    int32_t* n_valid;          // [n_pairs]
+    double fx, fy, cx, cy, half_patch;
+    int32_t width, height, n_pairs;
+};
+void launch_two_view_vote(const TwoViewArgs& a, hipStream_t s);
+void launch_two_view_finish(const TwoViewArgs& a, hipStream_t s);
+void launch_triangulate_dlt(const TwoViewArgs& a, hipStream_t s);
+// host half of the same path (two_view.hip)
+void two_view_fundamental(const svo_camera& cam, const double* E, double* F);
+void two_view_hypotheses(const double* E, double* hyp);
+double two_view_median(const double* depth, int64_t n);
+void two_view_rescale_pose(const double* ref_pose, double scale, double* cur_pose);
+
 // FeatureSelection (feature_select.hip)
 int feature_detect_segments(int64_t npx);
 void launch_feature_detect(const uint8_t* plane, int width, int height, int thr, int* seg_counts, uint32_t* keys,

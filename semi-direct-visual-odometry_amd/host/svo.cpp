@@ -404,6 +404,73 @@ void Map::removeMatchedCandidate() {  // src/map.cpp:629-634
                        m_candidates.end());
 }
 
+// ------------------------------------------------------------------ two-view map initialisation
+static void matched_pixels(const Frame& ref, const Frame& cur, std::vector<double>& refPx, std::vector<double>& curPx) {
+    const std::size_t n = ref.numberObservation();
+    if (cur.numberObservation() != n) throw Error(SVO_ERR_ARG, "svo: ref and cur frames hold different feature counts");
+    refPx.resize(2 * n);
+    curPx.resize(2 * n);
+    for (std::size_t i = 0; i < n; ++i)
+        for (int j = 0; j < 2; ++j) {
+            refPx[2 * i + j] = ref.m_features[i]->m_pixelPosition[j];
+            curPx[2 * i + j] = cur.m_features[i]->m_pixelPosition[j];
+        }
+}
+
+void algorithm::triangulate3DWorldPoints(Context& ctx, const std::shared_ptr<Frame>& refFrame,
+                                         const std::shared_ptr<Frame>& curFrame, std::vector<Vec3>& pointsWorld) {
+    std::vector<double> refPx, curPx;
+    matched_pixels(*refFrame, *curFrame, refPx, curPx);
+    const int32_t n = (int32_t)refFrame->numberObservation();
+    const int32_t off[2] = {0, n};
+    const svo_camera cam = refFrame->m_camera->c();
+    pointsWorld.resize((std::size_t)n);
+    check(svo_triangulate_dlt(ctx.get(), &cam, 1, off, refFrame->m_absPose.data(), curFrame->m_absPose.data(),
+                              refPx.data(), curPx.data(), n ? pointsWorld[0].data() : nullptr));
+}
+
+TwoViewResult initializeTwoView(Context& ctx, std::shared_ptr<Frame>& refFrame, std::shared_ptr<Frame>& curFrame,
+                                const std::array<double, 9>& E, double mapScale, int32_t cellPixelSize) {
+    std::vector<double> refPx, curPx;
+    matched_pixels(*refFrame, *curFrame, refPx, curPx);
+    const int32_t n = (int32_t)refFrame->numberObservation();
+    const int32_t off[2] = {0, n};
+    const svo_camera cam = refFrame->m_camera->c();
+    const std::size_t cap = n ? (std::size_t)n : 1;
+    std::vector<double> pointsWorld(3 * cap);
+    std::vector<uint8_t> valid(cap);
+    std::vector<int32_t> survivor(cap);
+    double F[9], median = 0.0;
+    int32_t nValid = 0;
+    TwoViewResult res;
+    Pose curPose = curFrame->m_absPose;
+    check(svo_two_view_init(ctx.get(), &cam, 1, off, E.data(), refFrame->m_absPose.data(), mapScale, cellPixelSize,
+                            refPx.data(), curPx.data(), F, res.counts.data(), &res.winner, curPose.data(), &median,
+                            &nValid, pointsWorld.data(), valid.data(), survivor.data(), nullptr));
+    for (int32_t i = 0; i < n; ++i) {  // sampsonCorrection (src/algorithm.cpp:233-234)
+        refFrame->m_features[i]->m_pixelPosition = {refPx[2 * i], refPx[2 * i + 1]};
+        curFrame->m_features[i]->m_pixelPosition = {curPx[2 * i], curPx[2 * i + 1]};
+    }
+    res.medianDepth = median;
+    if (res.winner < 0) return res;  // recoverPose failed (src/system.cpp:152-156)
+    res.ok = true;
+    curFrame->m_absPose = curPose;
+    for (int32_t k = 0; k < nValid; ++k) {  // (:201-209)
+        const int32_t i = survivor[k];
+        auto point = std::make_shared<Point>(Point{{pointsWorld[3 * i], pointsWorld[3 * i + 1], pointsWorld[3 * i + 2]}});
+        refFrame->m_features[i]->m_point = point;
+        curFrame->m_features[i]->m_point = point;
+        point->m_features.push_back(refFrame->m_features[i]);
+        point->m_features.push_back(curFrame->m_features[i]);
+    }
+    for (auto* fr : {refFrame.get(), curFrame.get()})  // (:217-223)
+        fr->m_features.erase(std::remove_if(fr->m_features.begin(), fr->m_features.end(),
+                                            [](const auto& feature) { return feature->m_point == nullptr; }),
+                             fr->m_features.end());
+    res.numPoints = (std::size_t)nValid;
+    return res;
+}
+
 // ------------------------------------------------------------------ trajectory / feature dump
 namespace utils {
 void writeInFile(const Pose& refAbsPose, std::ostream& w) {

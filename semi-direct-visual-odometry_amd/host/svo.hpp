@@ -235,6 +235,26 @@ private:
     int32_t m_cellSize, m_gridCols, m_gridRows;
 };
 
+// Two-view map initialisation (src/system.cpp:144-223 with src/algorithm.cpp:173-333, :553-599, :813-832).
+namespace algorithm {
+// triangulate3DWorldPoints (src/algorithm.cpp:553-566): feature i of refFrame against feature i of curFrame, with
+// the frames' current poses
+void triangulate3DWorldPoints(Context& ctx, const std::shared_ptr<Frame>& refFrame,
+                              const std::shared_ptr<Frame>& curFrame, std::vector<Vec3>& pointsWorld);
+}  // namespace algorithm
+struct TwoViewResult {
+    bool ok = false;             // recoverPose found a hypothesis with matches in front of both cameras
+    double medianDepth = 0.0;    // before scaling (NaN when !ok)
+    std::size_t numPoints = 0;   // points created = features left in each frame
+    std::array<int32_t, 4> counts{};  // cheirality vote of (R1,t) (R1,-t) (R2,t) (R2,-t)
+    int32_t winner = -1;
+};
+// What System::processSecondFrame does between computeEssentialMatrix and twoViewBA: Sampson-corrected
+// m_pixelPosition in both frames, curFrame->m_absPose, one Point per valid match linked both ways, and the features
+// without a point erased from both frames.  E is row-major.  !ok: only the pixels changed (src/system.cpp:152-156).
+TwoViewResult initializeTwoView(Context& ctx, std::shared_ptr<Frame>& refFrame, std::shared_ptr<Frame>& curFrame,
+                                const std::array<double, 9>& E, double mapScale, int32_t cellPixelSize);
+
 // Trajectory and feature-dump text, through std::ostream like the reference.
 namespace utils {
 // System::writeInFile (src/system.cpp:635-640): refAbsPose.inverse().matrix3x4() at precision 6

@@ -23,7 +23,13 @@
 //                                  cur pose (the second call reuses the object's batch); DATA.bin (doubles):
 //                                  fx fy cx cy W H, ref/kf/cur pose[7], n_ref n_kf, then per feature
 //                                  px[2] bearing[3] point[3] has_point; prints "err status pose[7]" per call
+//   svo_host_check init DATA.bin   initializeTwoView (GPU); DATA.bin (doubles): fx fy cx cy W H, ref pose[7], E[9]
+//                                  row-major, map_scale, cell, n, then n x (ref px[2] cur px[2]); prints
+//                                  "init ok winner c0 c1 c2 c3 n_points median", "pose" + cur pose[7], then per
+//                                  feature left "pt refx refy curx cury X Y Z" (no X Y Z when the call failed),
+//                                  then "tri X Y Z" per feature: algorithm::triangulate3DWorldPoints on the result
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -143,6 +149,59 @@ int main(int argc, char** argv) {
             std::printf("filters %zu\n", de.numberFilters());
             for (const auto& c : cands)
                 std::printf("cand %.17g %.17g %.17g\n", c.second->m_position[0], c.second->m_position[1], c.second->m_position[2]);
+            return 0;
+        }
+        if (mode == "init" && argc >= 3) {
+            std::ifstream f(argv[2], std::ios::binary);
+            f.seekg(0, std::ios::end);
+            const size_t bytes = (size_t)f.tellg();
+            f.seekg(0);
+            std::vector<double> v(bytes / sizeof(double));
+            f.read(reinterpret_cast<char*>(v.data()), (std::streamsize)bytes);
+            size_t q = 0;
+            auto take = [&]() { return v.at(q++); };
+            const double fx = take(), fy = take(), cx = take(), cy = take();
+            const int w = (int)take(), h = (int)take();
+            Pose refPose;
+            for (double& x : refPose) x = take();
+            std::array<double, 9> E;
+            for (double& x : E) x = take();
+            const double mapScale = take();
+            const int cell = (int)take(), n = (int)take();
+            Context ctx(0);
+            auto cam = std::make_shared<PinholeCamera>(PinholeCamera{w, h, fx, fy, cx, cy});
+            const std::vector<uint8_t> img((size_t)w * h, 0);
+            auto ref = std::make_shared<Frame>(ctx, cam, img.data(), 1);
+            auto cur = std::make_shared<Frame>(ctx, cam, img.data(), 1);
+            ref->m_absPose = refPose;
+            for (int i = 0; i < n; ++i) {
+                const double rx = take(), ry = take(), ux = take(), uy = take();
+                ref->m_features.push_back(std::make_shared<Feature>(ref.get(), Vec2{rx, ry}));
+                cur->m_features.push_back(std::make_shared<Feature>(cur.get(), Vec2{ux, uy}));
+            }
+            const TwoViewResult r = initializeTwoView(ctx, ref, cur, E, mapScale, cell);
+            std::printf("init %d %d %d %d %d %d %zu %.17g\n", r.ok ? 1 : 0, r.winner, r.counts[0], r.counts[1], r.counts[2],
+                        r.counts[3], r.numPoints, r.medianDepth);
+            std::printf("pose");
+            for (double x : cur->m_absPose) std::printf(" %.17g", x);
+            std::printf("\n");
+            for (size_t i = 0; i < ref->numberObservation(); ++i) {
+                const auto& fr = ref->m_features[i];
+                const auto& fc = cur->m_features[i];
+                if (r.ok && (fr->m_point != fc->m_point || fr->m_point->m_features.size() != 2))
+                    throw std::runtime_error("ref / cur features do not share their point");
+                std::printf("pt %.17g %.17g %.17g %.17g", fr->m_pixelPosition[0], fr->m_pixelPosition[1],
+                            fc->m_pixelPosition[0], fc->m_pixelPosition[1]);
+                if (fr->m_point)
+                    std::printf(" %.17g %.17g %.17g", fr->m_point->m_position[0], fr->m_point->m_position[1],
+                                fr->m_point->m_position[2]);
+                std::printf("\n");
+            }
+            if (r.ok) {  // triangulate3DWorldPoints on the initialised frames
+                std::vector<Vec3> tri;
+                algorithm::triangulate3DWorldPoints(ctx, ref, cur, tri);
+                for (const Vec3& x : tri) std::printf("tri %.17g %.17g %.17g\n", x[0], x[1], x[2]);
+            }
             return 0;
         }
         if (mode == "align" && argc >= 10) {
@@ -289,7 +348,7 @@ int main(int argc, char** argv) {
             if (reps > 0) std::printf("ms %.6f\n", total_ms / reps);
             return 0;
         }
-        std::fprintf(stderr, "usage: svo_host_check io | fs W H CELL THR NUM BUCKET IMAGE [EX EY]... | fv W H CELL THR IMAGE\n");
+        std::fprintf(stderr, "usage: svo_host_check io | fs W H CELL THR NUM BUCKET IMAGE [EX EY]... | fv W H CELL THR IMAGE | init DATA.bin\n");
         return 2;
     } catch (const std::exception& e) {
         std::fprintf(stderr, "svo_host_check: %s\n", e.what());

@@ -400,6 +400,53 @@ int svo_two_view_init(svo_ctx* ctx, const svo_camera* cam, int32_t n_pairs, cons
                       double* F, int32_t* counts, int32_t* winner, double* cur_poses, double* median_depth,
                       int32_t* n_valid, double* points_world, uint8_t* valid, int32_t* survivor, double* depth);
 
+/* ---------------------------------------------------------------- windowed bundle adjustment
+ * Replaces the optimisation inside BundleAdjustment::twoViewBA and ::localBA (src/bundle_adjustment.cpp:397-478,
+ * :480-625) for n_problems independent problems.  The reference hands these to g2o, which is not part of its tree;
+ * the cost and the schedule below are THIS PROJECT'S CONTRACT, modelled on g2o's OptimizationAlgorithmLevenberg
+ * with EdgeProjectXYZ2UV edges, and NOT pinned to g2o's bits.
+ *   problem    p owns frames frame_off[p] .. frame_off[p+1]-1 (at most SVO_BA_MAX_FRAMES, each free or fixed),
+ *              points point_off[p] .. (all free) and observations obs_off[p] .. (frame i, point j, pixel u; i and j
+ *              local to the problem).  Observations are grouped by point, points ascending, every point with at
+ *              least two and no (frame, point) twice.
+ *   residual   e = u - proj(T_i X_j), proj(c) = (f c.x / c.z + cx, f c.y / c.z + cy), f = cam->fx on BOTH axes
+ *              (setupG2o passes g2o::CameraParameters(fx, principalPoint, 0), :333: fy is never used); no
+ *              cheirality test
+ *   cost       Huber of width huber_delta on e2 = e.e: rho = e2 while sqrt(e2) <= delta, else
+ *              2 delta sqrt(e2) - delta^2; weight w = 1 or delta / sqrt(e2); information identity; chi = sum rho
+ *   step       pose <- exp(dp) * pose, dp = (upsilon; omega); X <- X + dx; with c = T_i X_j and A = d proj / d c:
+ *              J_p = A [I | -hat(c)], J_x = A R_i, H = sum w J^T J, b = sum w J^T e, (H + lambda I) dx = b, the
+ *              points eliminated first (Schur complement), Cholesky on the reduced system
+ *   schedule   lambda = 1e-5 * max diag(H) at the first linearisation, nu = 2.  Per iteration: cur = chi, build
+ *              H and b, then trials: solve, apply to a copy, tmp = chi(copy),
+ *              r = (cur - tmp) / (dx.(lambda dx + b) + 1e-3).  r > 0 and tmp finite: accept,
+ *              lambda *= max(1/3, min(1 - (2r-1)^3, 2/3)), nu = 2, next iteration.  Otherwise (also a non-positive
+ *              Cholesky pivot, recorded with r = 0 and chi = cur) lambda *= nu, nu *= 2; after 5 failed trials the
+ *              problem terminates.  At most max_iterations iterations (the reference passes 10).
+ *   structure  when structure_iterations > 0 every point is first adjusted on its own with all poses held
+ *              (StructureOnlySolver<3>::calc, :556-564): the same cost and schedule on its 3x3 system with its own
+ *              lambda and nu, a point that fails 5 trials stops
+ *   poses_inout  n_frames x 7, only free frames are written        frame_fixed  n_frames (uint8)
+ *   points_inout n_points x 3                                      obs_px       n_obs x 2
+ *   obs_chi2   n_obs: the non-robust e2 at the final estimate (edge->chi2(), :466, :603)
+ *   init_chi, final_chi  the robust sums before and after the joint run
+ *   iterations accepted iterations          status  0: ran max_iterations, 1: 5 failed trials, -1: no points
+ *              (a problem without points or frames leaves everything as given)
+ *   trace      NULL, or n_problems x SVO_BA_TRACE_CAP x 6: per trial (iteration, trial, accepted, lambda, r, chi) in
+ *              order; unused records have iteration -1, trials past the capacity are dropped
+ * A problem whose frames are all fixed is a structure-only problem (its reduced system is empty).  Every sum runs
+ * in an order fixed by the layout and no floating-point atomics are used: equal inputs give equal bytes.
+ * SVO_ERR_ARG: more than SVO_BA_MAX_FRAMES frames in a problem, observations not grouped by ascending point, a
+ * duplicate (frame, point), an index out of range, a point with fewer than two observations.  Synchronous. */
+#define SVO_BA_MAX_FRAMES 16
+#define SVO_BA_TRACE_CAP 64
+int svo_bundle_adjust(svo_ctx* ctx, const svo_camera* cam, int32_t n_problems, const int32_t* frame_off,
+                      const int32_t* point_off, const int32_t* obs_off, double* poses_inout,
+                      const uint8_t* frame_fixed, double* points_inout, const int32_t* obs_frame,
+                      const int32_t* obs_point, const double* obs_px, double huber_delta, int32_t max_iterations,
+                      int32_t structure_iterations, double* obs_chi2, double* init_chi, double* final_chi,
+                      int32_t* iterations, int32_t* status, double* trace);
+
 #ifdef __cplusplus
 }
 #endif

@@ -106,6 +106,9 @@ _SIGNATURES = [
     ("svo_two_view_init", c_int32, [c_void_p, ctypes.POINTER(SvoCamera), c_int32, c_void_p, c_void_p, c_void_p,
                                     c_double, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("svo_bundle_adjust", c_int32, [c_void_p, ctypes.POINTER(SvoCamera), c_int32, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_int32,
+                                    c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 ]
 
 EXPORTED = [s[0] for s in _SIGNATURES]

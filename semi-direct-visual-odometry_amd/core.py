@@ -292,6 +292,12 @@ class Point:
     def find_frame(self, frame):  # src/point.cpp: any observing feature in `frame`
         return any(f.frame is frame for f in self.features)
 
+    def remove_frame(self, frame):  # src/point.cpp:40-49: every observing feature that lies in `frame`
+        self.features = [f for f in self.features if f.frame is not frame]
+
+    def number_observation(self):  # src/point.cpp:113-116
+        return len(self.features)
+
     # a read-only float64 copy of the row (an in-place edit would not reach the table, so it raises instead).
     # Assigning it bumps a global version that invalidates every Frame's cached point array (a point is not told
     # which frames' features hold it).
@@ -472,6 +478,9 @@ class Frame:
 
     def add_feature(self, feature):
         self.features.append(feature)
+
+    def remove_feature(self, feature):  # src/frame.cpp:39-49 (one bump of the feature version)
+        self.features = [f for f in self.features if f is not feature]
 
     def number_observation(self):
         return len(self.features)
@@ -805,6 +814,25 @@ class Map:
     def cell_of(self, px):
         return int(px[1]) // self.cell_size * self.grid_cols + int(px[0]) // self.cell_size
 
+    def remove_point(self, point):  # src/map.cpp:76-87
+        for feature in point.features:
+            feature.frame.remove_feature(feature)
+        point.features.clear()
+        point.type = PointType.DELETED
+
+    def remove_feature(self, feature):  # src/map.cpp:89-110
+        point = feature.point
+        if point is None:
+            return
+        if point.number_observation() <= 2:
+            self.remove_point(point)
+            # removePoint nulls the shared_ptr it was handed, which is this feature's m_point (:86, :98); the
+            # feature is in no frame any more, so no frame's cached arrays hold it
+            feature._point, feature._pi = None, -1
+            return
+        point.remove_frame(feature.frame)
+        feature.frame.remove_feature(feature)  # the feature keeps its m_point (:108 is commented out)
+
     def reproject_map(self, ref_frame, cur_frame, overlap_keyframes):
         if ref_frame.last_keyframe is None:
             raise ValueError("reprojectMap needs refFrame->m_lastKeyframe")
@@ -1118,8 +1146,57 @@ def pose_optimize_batch(feat_off, bearing, point, has_point, vis, poses, ctx=Non
     return err, st
 
 
+class BundleAdjustResult:
+    """Outputs of bundle_adjust_batch (include/svo_c.h svo_bundle_adjust): obs_chi2 (n_obs,), init_chi, final_chi,
+    iterations, status (n_problems,), trace (n_problems, BA_TRACE_CAP, 6) or None."""
+    __slots__ = ("obs_chi2", "init_chi", "final_chi", "iterations", "status", "trace")
+
+
+BA_MAX_FRAMES = 16  # SVO_BA_MAX_FRAMES
+BA_TRACE_CAP = 64   # SVO_BA_TRACE_CAP
+
+
+def bundle_adjust_batch(camera, frame_off, point_off, obs_off, poses, frame_fixed, points, obs_frame, obs_point,
+                        obs_px, huber_delta, max_iterations=10, structure_iterations=0, trace=False, ctx=None):
+    """svo_bundle_adjust over arrays: the windowed bundle adjustment of twoViewBA / localBA
+    (src/bundle_adjustment.cpp:397-625) for independent problems.  The cost and the Levenberg-Marquardt schedule are
+    this project's contract (include/svo_c.h), modelled on g2o's and not pinned to it.  Problem p owns frames
+    frame_off[p]:frame_off[p+1], points point_off[p]:..., observations obs_off[p]:... (local indices, grouped by
+    point, points ascending).  poses ((n_frames, 7)) and points ((n_points, 3)), float64 and C-contiguous, are
+    updated in place."""
+    frame_off = np.ascontiguousarray(frame_off, np.int32)
+    point_off = np.ascontiguousarray(point_off, np.int32)
+    obs_off = np.ascontiguousarray(obs_off, np.int32)
+    if not (len(frame_off) == len(point_off) == len(obs_off) >= 1):
+        raise ValueError("frame_off, point_off and obs_off must hold n_problems + 1 entries each")
+    NP = len(frame_off) - 1
+    nf, nx, no = int(frame_off[-1]), int(point_off[-1]), int(obs_off[-1])
+    _c_f64(poses, (nf, 7), "poses")
+    _c_f64(points, (nx, 3), "points")
+    frame_fixed = np.ascontiguousarray(frame_fixed, np.uint8).reshape(nf)
+    obs_frame = np.ascontiguousarray(obs_frame, np.int32).reshape(no)
+    obs_point = np.ascontiguousarray(obs_point, np.int32).reshape(no)
+    obs_px = np.ascontiguousarray(obs_px, np.float64).reshape(no, 2)
+    r = BundleAdjustResult()
+    r.obs_chi2 = np.zeros(no)
+    r.init_chi = np.zeros(NP)
+    r.final_chi = np.zeros(NP)
+    r.iterations = np.zeros(NP, np.int32)
+    r.status = np.zeros(NP, np.int32)
+    r.trace = np.zeros((NP, BA_TRACE_CAP, 6)) if trace else None
+    cam = camera.as_c()
+    ctx = ctx or default_context()
+    check(lib().svo_bundle_adjust(ctx.handle, ctypes.byref(cam), NP, ptr(frame_off), ptr(point_off), ptr(obs_off),
+                                  ptr(poses), ptr(frame_fixed), ptr(points), ptr(obs_frame), ptr(obs_point),
+                                  ptr(obs_px), float(huber_delta), int(max_iterations), int(structure_iterations),
+                                  ptr(r.obs_chi2), ptr(r.init_chi), ptr(r.final_chi), ptr(r.iterations),
+                                  ptr(r.status), ptr(r.trace) if trace else None))
+    return r
+
+
 class BundleAdjustment:
-    """BundleAdjustment(camera, level, numParameters) — optimizePose (src/bundle_adjustment.cpp:30-166).
+    """BundleAdjustment(camera, level, numParameters) — optimizePose (src/bundle_adjustment.cpp:30-166), twoViewBA
+    (:397-478) and localBA (:480-625).
 
     ref_visibility is the member m_refVisibility: optimizePose's residual step reads the flags the
     previous call left (a fresh object returns NaN and moves nothing), see include/svo_c.h."""
@@ -1147,6 +1224,83 @@ class BundleAdjustment:
         frame.abs_pose = poses[0].copy()
         self.last_status = int(st[0])
         return float(err[0])
+
+    def _adjust(self, map_, frames, fixed, points, edges, reprojection_error, structure_iterations):
+        """The shared tail of two_view_ba / local_ba: one problem of `frames` (fixed flags), `points` and `edges`
+        (frame index, point index, feature; grouped by point), 10 iterations with Huber width reprojection_error;
+        poses of the free frames and all positions written back, then Map.remove_feature for every edge whose
+        e2 exceeds reprojection_error^2, in edge order.  Returns (init chi, final chi, edges over the threshold)."""
+        if len(frames) > BA_MAX_FRAMES:
+            raise ValueError(f"bundle adjustment over {len(frames)} frames (at most {BA_MAX_FRAMES})")
+        poses = np.array([np.asarray(f.abs_pose, np.float64).reshape(7) for f in frames], np.float64).reshape(-1, 7)
+        rows = np.fromiter((p._i for p in points), np.int64, count=len(points))
+        pos = np.ascontiguousarray(_PT.pos[rows], np.float64).reshape(-1, 3)
+        of = np.fromiter((e[0] for e in edges), np.int32, count=len(edges))
+        op = np.fromiter((e[1] for e in edges), np.int32, count=len(edges))
+        px = _rows([e[2].pixel_position for e in edges], 2) if edges else np.zeros((0, 2))
+        r = bundle_adjust_batch(self.camera, [0, len(frames)], [0, len(points)], [0, len(edges)], poses, fixed, pos,
+                                of, op, px, reprojection_error, 10, structure_iterations, False, self.ctx)
+        self.last_status = int(r.status[0])
+        for i, fr in enumerate(frames):
+            if not fixed[i]:
+                fr.abs_pose = poses[i].copy()
+        if len(points):  # every position in one assignment, one bump of the points' version
+            _PT.pos[rows] = pos
+            Point._ver += 1
+        over = np.nonzero(r.obs_chi2 > reprojection_error * reprojection_error)[0]
+        for k in over:  # (:461-476, :598-609)
+            map_.remove_feature(edges[k][2])
+        return float(r.init_chi[0]), float(r.final_chi[0]), len(over)
+
+    def two_view_ba(self, fst_frame, sec_frame, map, reprojection_error):
+        """twoViewBA (src/bundle_adjustment.cpp:397-478): fst_frame fixed, sec_frame free, one point vertex per
+        feature of fst_frame that has a point, its edge in fst_frame and the edge of Point::findFeature(sec_frame),
+        Huber width reprojection_error, 10 iterations; both poses and all positions written back, then
+        map.remove_feature for every edge with e2 > reprojection_error^2 in edge order."""
+        in_sec = {}
+        for f in sec_frame.features:  # Point::findFeature: the first feature of the frame that holds the point
+            if f.point is not None:
+                in_sec.setdefault(id(f.point), f)
+        points, edges = [], []
+        for f in fst_frame.features:
+            if f.point is None:
+                continue
+            g = in_sec.get(id(f.point))
+            if g is None:
+                raise ValueError("a point of the first frame is not observed in the second frame")
+            edges += [(0, len(points), f), (1, len(points), g)]
+            points.append(f.point)
+        return self._adjust(map, [fst_frame, sec_frame], np.array([1, 0], np.uint8), points, edges,
+                            reprojection_error, 0)
+
+    def local_ba(self, map, reprojection_error):
+        """localBA (src/bundle_adjustment.cpp:480-625): every frame of map.key_frames free; the points are those
+        with more than one observation that a keyframe observes; an observing frame outside the keyframe list
+        becomes a fixed frame; StructureOnlySolver first (10 iterations), then 10 joint iterations; write back;
+        map.remove_feature for every edge over the threshold.  The reference walks a std::set of shared_ptr, that
+        is, the points in pointer order; here they are taken in first-seen order (keyframe order, then feature
+        order), so the result does not depend on the allocator.  More than 16 frames in the problem raises."""
+        frames = list(map.key_frames)
+        index = {id(fr): i for i, fr in enumerate(frames)}
+        n_key = len(frames)
+        points, seen = [], set()
+        for fr in map.key_frames:
+            for f in fr.features:
+                p = f.point
+                if p is not None and p.number_observation() > 1 and id(p) not in seen:
+                    seen.add(id(p))
+                    points.append(p)
+        edges = []
+        for j, p in enumerate(points):
+            for f in p.features:
+                i = index.get(id(f.frame))
+                if i is None:  # a neighbour keyframe: fixed (:532-540)
+                    i = index[id(f.frame)] = len(frames)
+                    frames.append(f.frame)
+                edges.append((i, j, f))
+        fixed = np.zeros(len(frames), np.uint8)
+        fixed[n_key:] = 1
+        return self._adjust(map, frames, fixed, points, edges, reprojection_error, 10)
 
 
 # ---------------------------------------------------------------- two-view map initialisation

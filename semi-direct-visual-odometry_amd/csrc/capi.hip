@@ -1755,4 +1755,135 @@ int svo_two_view_init(svo_ctx* c, const svo_camera* cam, int32_t n_pairs, const 
     return SVO_OK;
 }
 
+// ------------------------------------------------------------------ windowed bundle adjustment
+static int ba_offsets(const char* what, int32_t n_problems, const int32_t* off) {
+    if (!off) return fail(SVO_ERR_ARG, "svo_bundle_adjust: null argument (%s)", what);
+    if (off[0] != 0) return fail(SVO_ERR_ARG, "svo_bundle_adjust: %s[0] must be 0", what);
+    for (int32_t p = 0; p < n_problems; ++p)
+        if (off[p + 1] < off[p]) return fail(SVO_ERR_ARG, "svo_bundle_adjust: %s not ascending at problem %d", what, p);
+    // (the structure kernel's grid spans max points / 256 in y: at most 65535)
+    if (off[n_problems] >= ((int32_t)1 << 24)) return fail(SVO_ERR_ARG, "svo_bundle_adjust: %s too large", what);
+    return SVO_OK;
+}
+
+int svo_bundle_adjust(svo_ctx* c, const svo_camera* cam, int32_t n_problems, const int32_t* frame_off,
+                      const int32_t* point_off, const int32_t* obs_off, double* poses_inout,
+                      const uint8_t* frame_fixed, double* points_inout, const int32_t* obs_frame,
+                      const int32_t* obs_point, const double* obs_px, double huber_delta, int32_t max_iterations,
+                      int32_t structure_iterations, double* obs_chi2, double* init_chi, double* final_chi,
+                      int32_t* iterations, int32_t* status, double* trace) {
+    if (n_problems < 0) return fail(SVO_ERR_ARG, "svo_bundle_adjust: n_problems < 0");
+    if (int r = ba_offsets("frame_off", n_problems, frame_off)) return r;
+    if (int r = ba_offsets("point_off", n_problems, point_off)) return r;
+    if (int r = ba_offsets("obs_off", n_problems, obs_off)) return r;
+    if (max_iterations < 0 || structure_iterations < 0)
+        return fail(SVO_ERR_ARG, "svo_bundle_adjust: negative iteration count");
+    if (!(huber_delta > 0.0) || !std::isfinite(huber_delta))
+        return fail(SVO_ERR_ARG, "svo_bundle_adjust: huber_delta must be positive and finite");
+    const size_t NP = (size_t)n_problems, NF = (size_t)frame_off[n_problems], NX = (size_t)point_off[n_problems],
+                 NO = (size_t)obs_off[n_problems];
+    if ((NP > 0 && (!init_chi || !final_chi || !iterations || !status)) ||
+        (NF > 0 && (!poses_inout || !frame_fixed)) || (NX > 0 && !points_inout) ||
+        (NO > 0 && (!obs_frame || !obs_point || !obs_px || !obs_chi2)))
+        return fail(SVO_ERR_ARG, "svo_bundle_adjust: null argument");
+    // layout: every point's observation block, checked before anything reaches the device
+    std::vector<int32_t> pobs(NX + 1, 0);
+    std::vector<int64_t> tab_off(NP + 1, 0);
+    int32_t max_points = 0;
+    for (size_t p = 0; p < NP; ++p) {
+        const int32_t F = frame_off[p + 1] - frame_off[p], P = point_off[p + 1] - point_off[p];
+        if (F > SVO_BA_MAX_FRAMES)
+            return fail(SVO_ERR_ARG, "svo_bundle_adjust: problem %zu has %d frames (at most %d)", p, F, SVO_BA_MAX_FRAMES);
+        tab_off[p + 1] = tab_off[p] + (int64_t)F * P;
+        max_points = std::max(max_points, P);
+        int32_t o = obs_off[p];
+        for (int32_t j = 0; j < P; ++j) {
+            pobs[(size_t)point_off[p] + j] = o;
+            uint32_t seen = 0;
+            while (o < obs_off[p + 1] && obs_point[o] == j) {
+                const int32_t i = obs_frame[o];
+                if (i < 0 || i >= F) return fail(SVO_ERR_ARG, "svo_bundle_adjust: observation %d: frame index out of range", o);
+                if (seen & (1u << i))
+                    return fail(SVO_ERR_ARG, "svo_bundle_adjust: observation %d: duplicate (frame, point)", o);
+                seen |= 1u << i;
+                ++o;
+            }
+            if (o - pobs[(size_t)point_off[p] + j] < 2)
+                return fail(SVO_ERR_ARG, "svo_bundle_adjust: problem %zu point %d has fewer than two observations "
+                                         "(observations must be grouped by ascending point)", p, j);
+        }
+        if (o != obs_off[p + 1])
+            return fail(SVO_ERR_ARG, "svo_bundle_adjust: observation %d: point index out of range or observations not "
+                                     "grouped by ascending point", o);
+    }
+    pobs[NX] = (int32_t)NO;
+    if (!c || !cam) return fail(SVO_ERR_ARG, "svo_bundle_adjust: null argument (ctx / cam)");
+    if (NP == 0) return SVO_OK;
+    SVO_HIP(hipSetDevice(c->device));
+    hipStream_t s = ctx_stream(c);
+    Carve cv;
+    const size_t o_fo = cv.take((NP + 1) * 4), o_po = cv.take((NP + 1) * 4), o_oo = cv.take((NP + 1) * 4),
+                 o_pobs = cv.take((NX + 1) * 4), o_to = cv.take((NP + 1) * 8), o_pose = cv.take(NF * 56),
+                 o_fix = cv.take(NF), o_pts = cv.take(NX * 24), o_of = cv.take(NO * 4), o_px = cv.take(NO * 16),
+                 o_tab = cv.take((size_t)tab_off[NP] * 4), o_edge = cv.take(NO * 120), o_W = cv.take(NO * 144),
+                 o_Vg = cv.take(NX * 72), o_Vi = cv.take(NX * 48), o_dx = cv.take(NX * 24), o_Xt = cv.take(NX * 24),
+                 o_chi2 = cv.take(NO * 8), o_ic = cv.take(NP * 8), o_fc = cv.take(NP * 8), o_it = cv.take(NP * 4),
+                 o_st = cv.take(NP * 4), o_tr = cv.take(trace ? NP * SVO_BA_TRACE_CAP * 48 : 0);
+    void* base = nullptr;
+    hipError_t e = ctx_scratch(c, cv.total, &base);
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, "bundle-adjust scratch: %s", hipGetErrorString(e));
+    char* db = static_cast<char*>(base);
+    struct Piece { size_t off; const void* src; size_t bytes; };
+    const Piece in[] = {{o_fo, frame_off, (NP + 1) * 4}, {o_po, point_off, (NP + 1) * 4}, {o_oo, obs_off, (NP + 1) * 4},
+                        {o_pobs, pobs.data(), (NX + 1) * 4}, {o_to, tab_off.data(), (NP + 1) * 8},
+                        {o_pose, poses_inout, NF * 56}, {o_fix, frame_fixed, NF}, {o_pts, points_inout, NX * 24},
+                        {o_of, obs_frame, NO * 4}, {o_px, obs_px, NO * 16}};
+    for (const Piece& pc : in)
+        if (e == hipSuccess) e = stage_copy(c, db + pc.off, pc.src, pc.bytes, hipMemcpyHostToDevice, s);
+    svo::BundleAdjustArgs a{};
+    a.frame_off = reinterpret_cast<int32_t*>(db + o_fo);
+    a.point_off = reinterpret_cast<int32_t*>(db + o_po);
+    a.obs_off = reinterpret_cast<int32_t*>(db + o_oo);
+    a.pobs_off = reinterpret_cast<int32_t*>(db + o_pobs);
+    a.tab_off = reinterpret_cast<int64_t*>(db + o_to);
+    a.poses = reinterpret_cast<double*>(db + o_pose);
+    a.frame_fixed = reinterpret_cast<uint8_t*>(db + o_fix);
+    a.points = reinterpret_cast<double*>(db + o_pts);
+    a.obs_frame = reinterpret_cast<int32_t*>(db + o_of);
+    a.obs_px = reinterpret_cast<double*>(db + o_px);
+    a.tab = reinterpret_cast<int32_t*>(db + o_tab);
+    a.edge = reinterpret_cast<double*>(db + o_edge);
+    a.W = reinterpret_cast<double*>(db + o_W);
+    a.Vg = reinterpret_cast<double*>(db + o_Vg);
+    a.Vi = reinterpret_cast<double*>(db + o_Vi);
+    a.dx = reinterpret_cast<double*>(db + o_dx);
+    a.Xt = reinterpret_cast<double*>(db + o_Xt);
+    a.obs_chi2 = reinterpret_cast<double*>(db + o_chi2);
+    a.init_chi = reinterpret_cast<double*>(db + o_ic);
+    a.final_chi = reinterpret_cast<double*>(db + o_fc);
+    a.iterations = reinterpret_cast<int32_t*>(db + o_it);
+    a.status = reinterpret_cast<int32_t*>(db + o_st);
+    a.trace = trace ? reinterpret_cast<double*>(db + o_tr) : nullptr;
+    a.f = cam->fx; a.cx = cam->cx; a.cy = cam->cy;  // fx on both axes (src/bundle_adjustment.cpp:333)
+    a.delta = huber_delta;
+    a.max_iterations = max_iterations;
+    a.structure_iterations = structure_iterations;
+    a.n_problems = n_problems;
+    a.max_points = max_points;
+    if (e == hipSuccess) {
+        svo::launch_ba_structure(a, s);
+        svo::launch_ba_joint(a, s);
+        e = hipGetLastError();
+    }
+    struct Out { size_t off; void* dst; size_t bytes; };
+    const Out out[] = {{o_pose, poses_inout, NF * 56}, {o_pts, points_inout, NX * 24}, {o_chi2, obs_chi2, NO * 8},
+                       {o_ic, init_chi, NP * 8}, {o_fc, final_chi, NP * 8}, {o_it, iterations, NP * 4},
+                       {o_st, status, NP * 4}, {o_tr, trace, trace ? NP * SVO_BA_TRACE_CAP * 48 : 0}};
+    for (const Out& o : out)
+        if (e == hipSuccess) e = stage_copy(c, o.dst, db + o.off, o.bytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, "svo_bundle_adjust: %s", hipGetErrorString(e));
+    return SVO_OK;
+}
+
 }  // extern "C"

@@ -223,6 +223,38 @@ void two_view_hypotheses(const double* E, double* hyp);
 double two_view_median(const double* depth, int64_t n);
 void two_view_rescale_pose(const double* ref_pose, double scale, double* cur_pose);
 
+struct BundleAdjustArgs {  // windowed bundle adjustment over a batch of problems (bundle_adjust.hip)
+    const int32_t* frame_off;   // [n_problems + 1]
+    const int32_t* point_off;   // [n_problems + 1]
+    const int32_t* obs_off;     // [n_problems + 1]
+    const int32_t* pobs_off;    // [n_points + 1] first observation (global index) of every point (global index)
+    const int64_t* tab_off;     // [n_problems + 1] start of each problem's frames x points table in `tab`
+    double* poses;              // [n_frames][7] in/out
+    const uint8_t* frame_fixed; // [n_frames]
+    double* points;             // [n_points][3] in/out
+    const int32_t* obs_frame;   // [n_obs] local frame index
+    const double* obs_px;       // [n_obs][2]
+    // scratch
+    int32_t* tab;               // per problem [P][F]: the observation (local index) of point j in frame i, or -1
+    double* edge;               // [n_obs][15] J_p (2 x 6), e (2), w of the current linearisation
+    double* W;                  // [n_obs][18] w J_p^T J_x (6 x 3)
+    double* Vg;                 // [n_points][9] V_j (xx xy xz yy yz zz), g_j
+    double* Vi;                 // [n_points][6] (V_j + lambda I)^-1
+    double* dx;                 // [n_points][3] the trial's point step
+    double* Xt;                 // [n_points][3] the trial's points
+    // outputs
+    double* obs_chi2;           // [n_obs]
+    double* init_chi;           // [n_problems]
+    double* final_chi;          // [n_problems]
+    int32_t* iterations;        // [n_problems]
+    int32_t* status;            // [n_problems]
+    double* trace;              // [n_problems][SVO_BA_TRACE_CAP][6] or nullptr
+    double f, cx, cy, delta;
+    int32_t max_iterations, structure_iterations, n_problems, max_points;
+};
+void launch_ba_structure(const BundleAdjustArgs& a, hipStream_t s);
+void launch_ba_joint(const BundleAdjustArgs& a, hipStream_t s);
+
 // FeatureSelection (feature_select.hip)
 int feature_detect_segments(int64_t npx);
 void launch_feature_detect(const uint8_t* plane, int width, int height, int thr, int* seg_counts, uint32_t* keys,

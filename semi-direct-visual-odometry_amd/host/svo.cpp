@@ -404,6 +404,120 @@ void Map::removeMatchedCandidate() {  // src/map.cpp:629-634
                        m_candidates.end());
 }
 
+// ------------------------------------------------------------------ windowed bundle adjustment
+void Point::removeFrame(const Frame* frame) {  // src/point.cpp:40-49
+    m_features.erase(std::remove_if(m_features.begin(), m_features.end(),
+                                    [frame](const std::weak_ptr<Feature>& w) {
+                                        const auto f = w.lock();
+                                        return f && f->m_frame == frame;
+                                    }),
+                     m_features.end());
+}
+
+void Frame::removeFeature(const std::shared_ptr<Feature>& feature) {  // src/frame.cpp:39-49
+    m_features.erase(std::remove(m_features.begin(), m_features.end(), feature), m_features.end());
+}
+
+void removePoint(std::shared_ptr<Point>& point) {  // src/map.cpp:76-87
+    const std::shared_ptr<Point> keep = point;  // (`point` may be the m_point of a feature about to leave its frame)
+    for (auto& w : keep->m_features)
+        if (const auto feature = w.lock()) feature->m_frame->removeFeature(feature);
+    keep->m_features.clear();
+    keep->m_type = Point::PointType::DELETED;
+    point = nullptr;
+}
+
+void removeFeature(std::shared_ptr<Feature>& feature) {  // src/map.cpp:89-110
+    if (feature->m_point == nullptr) return;
+    if (feature->m_point->numberObservation() <= 2) {
+        removePoint(feature->m_point);
+        return;
+    }
+    feature->m_point->removeFrame(feature->m_frame);
+    feature->m_frame->removeFeature(feature);
+    feature = nullptr;
+}
+
+BundleAdjustment::WindowResult BundleAdjustment::adjust(const std::vector<Frame*>& frames, const std::vector<uint8_t>& fixed,
+                                                        const std::vector<std::shared_ptr<Point>>& points,
+                                                        std::vector<Edge>& edges, double reprojectionError,
+                                                        int32_t structureIterations) {
+    if (frames.size() > SVO_BA_MAX_FRAMES) throw Error(SVO_ERR_ARG, "svo: bundle adjustment over more than 16 frames");
+    const int32_t frameOff[2] = {0, (int32_t)frames.size()}, pointOff[2] = {0, (int32_t)points.size()},
+                  obsOff[2] = {0, (int32_t)edges.size()};
+    std::vector<double> poses(7 * frames.size()), pos(3 * points.size()), px(2 * edges.size()), chi2(edges.size());
+    std::vector<int32_t> of(edges.size()), op(edges.size());
+    for (std::size_t i = 0; i < frames.size(); ++i) std::copy(frames[i]->m_absPose.begin(), frames[i]->m_absPose.end(), &poses[7 * i]);
+    for (std::size_t j = 0; j < points.size(); ++j) std::copy(points[j]->m_position.begin(), points[j]->m_position.end(), &pos[3 * j]);
+    for (std::size_t k = 0; k < edges.size(); ++k) {
+        of[k] = edges[k].frame;
+        op[k] = edges[k].point;
+        px[2 * k] = edges[k].feature->m_pixelPosition[0];
+        px[2 * k + 1] = edges[k].feature->m_pixelPosition[1];
+    }
+    const svo_camera cam = m_camera->c();
+    WindowResult res;
+    int32_t iterations = 0;
+    check(svo_bundle_adjust(m_ctx.get(), &cam, 1, frameOff, pointOff, obsOff, poses.data(), fixed.data(), pos.data(),
+                            of.data(), op.data(), px.data(), reprojectionError, 10, structureIterations, chi2.data(),
+                            &res.initError, &res.finalError, &iterations, &m_status, nullptr));
+    for (std::size_t i = 0; i < frames.size(); ++i)
+        if (!fixed[i]) std::copy(&poses[7 * i], &poses[7 * i] + 7, frames[i]->m_absPose.begin());
+    for (std::size_t j = 0; j < points.size(); ++j) std::copy(&pos[3 * j], &pos[3 * j] + 3, points[j]->m_position.begin());
+    const double chiSquaredError = reprojectionError * reprojectionError;
+    for (std::size_t k = 0; k < edges.size(); ++k)  // (:461-476, :598-609)
+        if (chi2[k] > chiSquaredError) {
+            removeFeature(edges[k].feature);
+            ++res.removed;
+        }
+    return res;
+}
+
+BundleAdjustment::WindowResult BundleAdjustment::twoViewBA(std::shared_ptr<Frame>& fstFrame, std::shared_ptr<Frame>& secFrame,
+                                                           double reprojectionError) {
+    std::vector<std::shared_ptr<Point>> points;
+    std::vector<Edge> edges;
+    for (auto& feature : fstFrame->m_features) {
+        if (feature->m_point == nullptr) continue;
+        std::shared_ptr<Feature> inSec;  // Point::findFeature(secFrame)
+        for (auto& f : secFrame->m_features)
+            if (f->m_point == feature->m_point) { inSec = f; break; }
+        if (!inSec) throw Error(SVO_ERR_ARG, "svo: a point of the first frame is not observed in the second frame");
+        edges.push_back({0, (int32_t)points.size(), feature});
+        edges.push_back({1, (int32_t)points.size(), inSec});
+        points.push_back(feature->m_point);
+    }
+    return adjust({fstFrame.get(), secFrame.get()}, {1, 0}, points, edges, reprojectionError, 0);
+}
+
+BundleAdjustment::WindowResult BundleAdjustment::localBA(std::vector<std::shared_ptr<Frame>>& keyFrames, double reprojectionError) {
+    std::vector<Frame*> frames;
+    for (auto& kf : keyFrames) frames.push_back(kf.get());
+    const std::size_t nKey = frames.size();
+    std::vector<std::shared_ptr<Point>> points;
+    for (auto& kf : keyFrames)
+        for (auto& feature : kf->m_features) {
+            const auto& p = feature->m_point;
+            if (p != nullptr && p->numberObservation() > 1 && std::find(points.begin(), points.end(), p) == points.end())
+                points.push_back(p);
+        }
+    std::vector<Edge> edges;
+    for (std::size_t j = 0; j < points.size(); ++j)
+        for (auto& w : points[j]->m_features) {
+            const auto feature = w.lock();
+            if (!feature) throw Error(SVO_ERR_STATE, "svo: a point is observed by a feature no frame holds");
+            auto it = std::find(frames.begin(), frames.end(), feature->m_frame);
+            if (it == frames.end()) {  // a neighbour keyframe: fixed (:532-540)
+                frames.push_back(feature->m_frame);
+                it = frames.end() - 1;
+            }
+            edges.push_back({(int32_t)(it - frames.begin()), (int32_t)j, feature});
+        }
+    std::vector<uint8_t> fixed(frames.size(), 0);
+    std::fill(fixed.begin() + (std::ptrdiff_t)nKey, fixed.end(), (uint8_t)1);
+    return adjust(frames, fixed, points, edges, reprojectionError, 10);
+}
+
 // ------------------------------------------------------------------ two-view map initialisation
 static void matched_pixels(const Frame& ref, const Frame& cur, std::vector<double>& refPx, std::vector<double>& curPx) {
     const std::size_t n = ref.numberObservation();

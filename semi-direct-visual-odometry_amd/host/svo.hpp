@@ -86,6 +86,8 @@ struct Point {  // include/point.hpp:14-40 (the members the map's reprojection r
     uint32_t m_succeededProjection = 0;
     uint32_t m_failedProjection = 0;
     std::vector<std::weak_ptr<Feature>> m_features;  // observing features (weak: Frame owns them)
+    std::size_t numberObservation() const { return m_features.size(); }  // src/point.cpp:113-116
+    void removeFrame(const Frame* frame);                                 // src/point.cpp:40-49
 };
 struct Feature {  // include/feature.hpp:14
     enum class FeatureType : uint32_t { EDGE = 0, CORNER = 1 };  // include/feature.hpp:19-23
@@ -108,7 +110,11 @@ struct Frame {  // include/frame.hpp:70-208 (the members the alignment path read
     std::shared_ptr<Frame> m_lastKeyframe;
     uint64_t m_id;  // Frame::m_frameCounter (src/frame.cpp:6-27)
     std::size_t numberObservation() const { return m_features.size(); }
+    void removeFeature(const std::shared_ptr<Feature>& feature);  // src/frame.cpp:39-49
 };
+// Map::removePoint / Map::removeFeature (src/map.cpp:76-110); they touch no member of the map
+void removePoint(std::shared_ptr<Point>& point);
+void removeFeature(std::shared_ptr<Feature>& feature);
 
 // ImageAlignment (include/image_alignment.hpp:15-73)
 // medianMode: SVO_MEDIAN_REFERENCE (default) reproduces the reference's robust scale bit for bit.
@@ -178,8 +184,18 @@ public:
     double optimizePose(std::shared_ptr<Frame>& frame);
     int32_t lastStatus() const { return m_status; }
     const std::vector<uint8_t>& refVisibility() const { return m_refVisibility; }
+    // twoViewBA (:397-478) and localBA (:480-625) over svo_bundle_adjust: the cost and the schedule are this
+    // project's contract (include/svo_c.h), modelled on g2o's and not pinned to it.  localBA takes the points in
+    // first-seen order (keyframe order, then feature order) where the reference walks a std::set of pointers.
+    struct WindowResult { double initError = 0.0, finalError = 0.0; uint32_t removed = 0; };
+    WindowResult twoViewBA(std::shared_ptr<Frame>& fstFrame, std::shared_ptr<Frame>& secFrame, double reprojectionError);
+    WindowResult localBA(std::vector<std::shared_ptr<Frame>>& keyFrames, double reprojectionError);
 
 private:
+    struct Edge { int32_t frame, point; std::shared_ptr<Feature> feature; };
+    WindowResult adjust(const std::vector<Frame*>& frames, const std::vector<uint8_t>& fixed,
+                        const std::vector<std::shared_ptr<Point>>& points, std::vector<Edge>& edges,
+                        double reprojectionError, int32_t structureIterations);
     Context& m_ctx;
     std::shared_ptr<PinholeCamera> m_camera;
     std::vector<uint8_t> m_refVisibility;

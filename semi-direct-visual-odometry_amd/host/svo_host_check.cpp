@@ -28,6 +28,13 @@
 //                                  "init ok winner c0 c1 c2 c3 n_points median", "pose" + cur pose[7], then per
 //                                  feature left "pt refx refy curx cury X Y Z" (no X Y Z when the call failed),
 //                                  then "tri X Y Z" per feature: algorithm::triangulate3DWorldPoints on the result
+//   svo_host_check wba DATA.bin    BundleAdjustment::twoViewBA / localBA (GPU; `ba` is optimizePose above); DATA.bin
+//                                  (doubles): fx fy cx cy W H, reprojection error, local (0: twoViewBA of frames 0
+//                                  and 1, 1: localBA), n_key, n_frames, n_frames x pose[7], n_points, n_points x X[3],
+//                                  n_edges, n_edges x (frame point px py): one Feature per edge, appended to its frame
+//                                  and to its point in edge order, the first n_key frames the keyframes; prints with
+//                                  %a "chi init final removed", per frame "pose p[7]" and "left n", per point
+//                                  "pt X Y Z type observations"
 #include <algorithm>
 #include <array>
 #include <chrono>
@@ -204,6 +211,58 @@ int main(int argc, char** argv) {
             }
             return 0;
         }
+        if (mode == "wba" && argc >= 3) {
+            std::ifstream f(argv[2], std::ios::binary);
+            f.seekg(0, std::ios::end);
+            const size_t bytes = (size_t)f.tellg();
+            f.seekg(0);
+            std::vector<double> v(bytes / sizeof(double));
+            f.read(reinterpret_cast<char*>(v.data()), (std::streamsize)bytes);
+            size_t q = 0;
+            auto take = [&]() { return v.at(q++); };
+            const double fx = take(), fy = take(), cx = take(), cy = take();
+            const int w = (int)take(), h = (int)take();
+            const double reproj = take();
+            const bool local = take() != 0.0;
+            const int nKey = (int)take(), nFrames = (int)take();
+            Context ctx(0);
+            auto cam = std::make_shared<PinholeCamera>(PinholeCamera{w, h, fx, fy, cx, cy});
+            const std::vector<uint8_t> img((size_t)w * h, 0);
+            std::vector<std::shared_ptr<Frame>> frames;
+            for (int i = 0; i < nFrames; ++i) {
+                frames.push_back(std::make_shared<Frame>(ctx, cam, img.data(), 1));
+                for (double& x : frames.back()->m_absPose) x = take();
+            }
+            std::vector<std::shared_ptr<Point>> points;
+            const int nPoints = (int)take();
+            for (int j = 0; j < nPoints; ++j) {
+                const double x = take(), y = take(), z = take();
+                points.push_back(std::make_shared<Point>(Point{{x, y, z}}));
+            }
+            const int nEdges = (int)take();
+            for (int k = 0; k < nEdges; ++k) {
+                const int i = (int)take(), j = (int)take();
+                const double px = take(), py = take();
+                auto feature = std::make_shared<Feature>(frames.at(i).get(), Vec2{px, py});
+                feature->m_point = points.at(j);
+                points[j]->m_features.push_back(feature);
+                frames[i]->m_features.push_back(feature);
+            }
+            BundleAdjustment bundler(ctx, cam, 0, 6);
+            std::vector<std::shared_ptr<Frame>> keyFrames(frames.begin(), frames.begin() + nKey);
+            const BundleAdjustment::WindowResult r =
+                local ? bundler.localBA(keyFrames, reproj) : bundler.twoViewBA(frames.at(0), frames.at(1), reproj);
+            std::printf("chi %a %a %u\n", r.initError, r.finalError, r.removed);
+            for (const auto& fr : frames) {
+                std::printf("pose");
+                for (double x : fr->m_absPose) std::printf(" %a", x);
+                std::printf("\nleft %zu\n", fr->numberObservation());
+            }
+            for (const auto& p : points)
+                std::printf("pt %a %a %a %u %zu\n", p->m_position[0], p->m_position[1], p->m_position[2],
+                            (unsigned)p->m_type, p->numberObservation());
+            return 0;
+        }
         if (mode == "align" && argc >= 10) {
             std::ifstream f(argv[2], std::ios::binary);
             f.seekg(0, std::ios::end);
@@ -348,7 +407,7 @@ int main(int argc, char** argv) {
             if (reps > 0) std::printf("ms %.6f\n", total_ms / reps);
             return 0;
         }
-        std::fprintf(stderr, "usage: svo_host_check io | fs W H CELL THR NUM BUCKET IMAGE [EX EY]... | fv W H CELL THR IMAGE | init DATA.bin\n");
+        std::fprintf(stderr, "usage: svo_host_check io | fs W H CELL THR NUM BUCKET IMAGE [EX EY]... | fv W H CELL THR IMAGE | init DATA.bin | wba DATA.bin\n");
         return 2;
     } catch (const std::exception& e) {
         std::fprintf(stderr, "svo_host_check: %s\n", e.what());

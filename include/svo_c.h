@@ -447,6 +447,63 @@ int svo_bundle_adjust(svo_ctx* ctx, const svo_camera* cam, int32_t n_problems, c
                       int32_t structure_iterations, double* obs_chi2, double* init_chi, double* final_chi,
                       int32_t* iterations, int32_t* status, double* trace);
 
+/* ---------------------------------------------------------------- sparse optical flow (pyramidal Lucas-Kanade)
+ * Replaces the tracking inside algorithm::computeOpticalFlowSparse (src/algorithm.cpp:29-107, called
+ * src/system.cpp:128-129), which hands the two base images to cv::calcOpticalFlowPyrLK (window patchSize^2, maxLevel 3,
+ * 30 iterations, eps 1e-4, OPTFLOW_USE_INITIAL_FLOW), for n_pairs independent frame pairs.  OpenCV is not part of the
+ * reference tree; the arithmetic below is THIS PROJECT'S CONTRACT, modelled on calcOpticalFlowPyrLK and NOT pinned to
+ * OpenCV's bits.  The pyramid is the intensity stack of svo_pyramid_set_build (level l = pyrDown of level l-1).
+ *   ref_set, cur_set  two pyramid sets of equal geometry; frames: n_pairs x 2 frame indices (ref in ref_set, cur in
+ *                     cur_set)
+ *   feat_off   n_pairs + 1, laid out as for svo_triangulate_dlt: pair p owns points feat_off[p] .. feat_off[p+1]-1
+ *   ref_px     n x 2
+ *   cur_px     n x 2, in: the initial flow (the reference passes the ref positions); out: the tracked positions
+ *   status     n (uint8): 1 tracked, 0 lost
+ *   trace      NULL, or n x (max_level+1) x 2 int32: per level l (index l) the iterations run (steps computed) and an
+ *              exit code: 0 level skipped (above L, below), 1 eps, 2 oscillation, 3 iteration limit, 4 left the
+ *              image, 5 template out of range, 6 min-eigenvalue / determinant reject
+ *   median_disparity  NULL, or n_pairs: algorithm::computeMedian (src/algorithm.cpp:813-832, a real std::nth_element)
+ *              of the pair's disparities (:74): per tracked point the double norm of the float32 differences
+ *              ref.x - cur.x, ref.y - cur.y of the float32 positions; NaN for a pair without tracked points
+ * Per point, with h = (win - 1) / 2, W_l x H_l the size of level l and I / J the ref / cur intensity planes:
+ *   1 ref_px and the initial cur_px are rounded to float32 (the reference's static_cast<float>); all later state is
+ *     double.
+ *   2 L is the largest l <= max_level with W_l > win and H_l > win (0 if there is none).  Levels L .. 0 are processed;
+ *     the flow starts as cur / 2^L and is doubled between levels.
+ *   3 template: p = ref / 2^l - h, ip = floor(p), (a, b) = p - ip.  Unless -win <= ip.x < W_l and -win <= ip.y < H_l:
+ *     exit 5; at level 0 status = 0, at another level the level is skipped and the flow carries on.
+ *     iw00 = rint((1-a)(1-b) 2^14), iw01 = rint(a (1-b) 2^14), iw10 = rint((1-a) b 2^14) (ties to even),
+ *     iw11 = 2^14 - iw00 - iw01 - iw10; descale(v, k) = (v + 2^(k-1)) >> k (arithmetic shift).
+ *     For the win^2 pixels (x, y), 0 <= x, y < win, at X = ip.x + x, Y = ip.y + y:
+ *       S(F) = iw00 F(X, Y) + iw01 F(X+1, Y) + iw10 F(X, Y+1) + iw11 F(X+1, Y+1)
+ *       T = descale(S(I), 9) (5 extra bits); I outside the image is BORDER_REFLECT_101 (one reflection, then clamped)
+ *       Ix(X, Y) = 3 (I(X+1,Y-1) - I(X-1,Y-1)) + 10 (I(X+1,Y) - I(X-1,Y)) + 3 (I(X+1,Y+1) - I(X-1,Y+1)) (Scharr), Iy
+ *       likewise with the axes exchanged, REFLECT_101 inside the 3x3; Ix = Iy = 0 where (X, Y) is outside the image
+ *       gx = descale(S(Ix), 14), gy = descale(S(Iy), 14)
+ *   4 A11 = sum gx^2, A12 = sum gx gy, A22 = sum gy^2: exact 64-bit integer sums, then converted to double and
+ *     multiplied by 2^-20.  D = A11 A22 - A12 A12,
+ *     minEig = (A22 + A11 - sqrt((A11 - A22)(A11 - A22) + 4 A12 A12)) / (2 win^2).
+ *     minEig < min_eig_threshold or D < FLT_EPSILON: exit 6, status as in step 3.
+ *   5 q = flow - h, prev = (0, 0); for j < max_iterations: iq = floor(q); the range test of step 3 on iq, failing:
+ *     exit 4, status = 0 at level 0.  With the weights of q - iq: d = descale(S(J), 9) - T per pixel;
+ *     b1 = sum d gx, b2 = sum d gy (exact 64-bit integer sums) times 2^-20;
+ *     delta = ((A12 b2 - A22 b1) (1 / D), (A12 b1 - A11 b2) (1 / D)); q += delta.
+ *     delta.delta <= epsilon^2: exit 1.  j > 0 and |delta.x + prev.x| < 0.01 and |delta.y + prev.y| < 0.01:
+ *     q -= delta / 2, exit 2.  Otherwise prev = delta.  j reaching max_iterations: exit 3.
+ *     The flow becomes q + h (also after exit 4).
+ *   6 cur_px = the level-0 flow rounded to float32 and widened (what a cv::Point2f holds), written for every point;
+ *     status = 1 unless cleared above.
+ * Every sum is over integers and the double tail uses IEEE add, multiply, divide and sqrt only (no contraction), so
+ * equal inputs give equal bytes, equal to a CPU restatement.
+ * SVO_ERR_ARG: win even, < 3 or > SVO_KLT_MAX_WIN, max_level < 0 (these before anything else is looked at),
+ * max_level >= the sets' level count, sets of different geometry, a frame index out of range.  Waits for a pending
+ * svo_pyramid_set_build_async of either set and for pending alignment chains.  Synchronous. */
+#define SVO_KLT_MAX_WIN 21
+int svo_klt_track(svo_ctx* ctx, const svo_pyramid_set* ref_set, const svo_pyramid_set* cur_set, int32_t n_pairs,
+                  const int32_t* frames, const int32_t* feat_off, const double* ref_px, double* cur_px, int32_t win,
+                  int32_t max_level, int32_t max_iterations, double epsilon, double min_eig_threshold, uint8_t* status,
+                  int32_t* trace, double* median_disparity);
+
 #ifdef __cplusplus
 }
 #endif

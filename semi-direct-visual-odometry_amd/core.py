@@ -1405,3 +1405,46 @@ def two_view_initialize(ref_frame, cur_frame, E, map_scale, cell_size, ctx=None)
     for fr in (ref_frame, cur_frame):  # remove_if(m_point == nullptr) (:217-223)
         fr.features = [f for f in fr.features if f.point is not None]
     return True, float(r.median_depth[0]), int(r.n_valid[0])
+
+
+# ---------------------------------------------------------------- sparse optical flow (pyramidal Lucas-Kanade)
+def klt_track_batch(ref_set, cur_set, frames, feat_off, ref_px, cur_px, win=11, max_level=3, max_iterations=30,
+                    epsilon=1e-4, min_eig_threshold=1e-4, trace=False, ctx=None):
+    """svo_klt_track over arrays: pair p tracks points feat_off[p]:feat_off[p+1] from frame frames[p][0] of ref_set
+    into frame frames[p][1] of cur_set, starting at cur_px (the initial flow; not modified).  Returns (cur (n, 2),
+    status (n,) uint8, median_disparity (P,)), and the per-level trace (n, max_level + 1, 2) int32 last with
+    trace=True (include/svo_c.h lists the exit codes)."""
+    ctx = ctx or default_context()
+    feat_off = np.ascontiguousarray(feat_off, np.int32)
+    P = len(feat_off) - 1
+    n = int(feat_off[-1]) if P >= 0 else 0
+    frames = np.ascontiguousarray(frames, np.int32).reshape(P, 2)
+    ref_px = np.ascontiguousarray(ref_px, np.float64).reshape(n, 2)
+    cur = np.array(cur_px, np.float64).reshape(n, 2)
+    status = np.zeros(n, np.uint8)
+    median = np.zeros(P)
+    tr = np.zeros((n, max(int(max_level), 0) + 1, 2), np.int32) if trace else None
+    check(lib().svo_klt_track(ctx.handle, ref_set.handle, cur_set.handle, P, ptr(frames), ptr(feat_off), ptr(ref_px),
+                              ptr(cur), int(win), int(max_level), int(max_iterations), float(epsilon),
+                              float(min_eig_threshold), ptr(status), ptr(tr), ptr(median)))
+    return (cur, status, median, tr) if trace else (cur, status, median)
+
+
+def compute_optical_flow_sparse(ref_frame, cur_frame, patch_size, disparity_threshold, ctx=None):
+    """algorithm::computeOpticalFlowSparse(refFrame, curFrame, patchSize, disparityThreshold)
+    (src/algorithm.cpp:29-107): the ref frame's features tracked into the cur frame (window patch_size, 4 levels, 30
+    iterations, eps 1e-4, initial flow = the ref positions); a Feature(cur, px, 0.0, 0.0, 0) is added to cur_frame
+    per tracked point, in order; False when the median disparity is below the threshold (the cur features stay, the
+    ref frame is untouched: the reference's own order); otherwise the untracked features leave ref_frame (order
+    kept) and the result is True.  No tracked point gives a NaN median and hence True, as in the reference."""
+    n = ref_frame.number_observation()
+    ref_px = np.array(ref_frame.feature_arrays()[0], np.float64).reshape(n, 2)
+    cur, status, median = klt_track_batch(ref_frame.image_pyramid.set, cur_frame.image_pyramid.set, [[0, 0]], [0, n],
+                                          ref_px, ref_px, int(patch_size), 3, 30, 1e-4, ctx=ctx)[:3]
+    tracked = status == 1
+    new = Feature._many(cur_frame, cur[tracked], level=0, gradient_magnitude=[0.0] * int(tracked.sum()))
+    cur_frame.features.extend(new)
+    if median[0] < disparity_threshold:
+        return False
+    ref_frame.features = [f for f, t in zip(ref_frame.features, tracked) if t]
+    return True

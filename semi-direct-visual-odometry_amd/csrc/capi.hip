@@ -1886,4 +1886,92 @@ int svo_bundle_adjust(svo_ctx* c, const svo_camera* cam, int32_t n_problems, con
     return SVO_OK;
 }
 
+// ------------------------------------------------------------------ sparse optical flow (pyramidal Lucas-Kanade)
+int svo_klt_track(svo_ctx* c, const svo_pyramid_set* ref_set, const svo_pyramid_set* cur_set, int32_t n_pairs,
+                  const int32_t* frames, const int32_t* feat_off, const double* ref_px, double* cur_px, int32_t win,
+                  int32_t max_level, int32_t max_iterations, double epsilon, double min_eig_threshold, uint8_t* status,
+                  int32_t* trace, double* median_disparity) {
+    // the scalar parameters first: these need neither a context nor a set
+    if (win < 3 || win > SVO_KLT_MAX_WIN || win % 2 == 0)
+        return fail(SVO_ERR_ARG, "svo_klt_track: win %d must be odd and within 3..%d", win, SVO_KLT_MAX_WIN);
+    if (max_level < 0) return fail(SVO_ERR_ARG, "svo_klt_track: max_level < 0");
+    if (max_iterations < 0) return fail(SVO_ERR_ARG, "svo_klt_track: max_iterations < 0");
+    int64_t n = 0;
+    if (int r = two_view_check("svo_klt_track", n_pairs, feat_off, &n)) return r;
+    if (!c || !ref_set || !cur_set || (n_pairs > 0 && !frames) || (n > 0 && (!ref_px || !cur_px || !status)))
+        return fail(SVO_ERR_ARG, "svo_klt_track: null argument");
+    if (ref_set->ctx != c || cur_set->ctx != c) return fail(SVO_ERR_ARG, "svo_klt_track: pyramid set belongs to another context");
+    if (ref_set->width != cur_set->width || ref_set->height != cur_set->height || ref_set->levels != cur_set->levels)
+        return fail(SVO_ERR_ARG, "svo_klt_track: the sets differ in geometry (%dx%d, %d levels vs %dx%d, %d levels)",
+                    ref_set->width, ref_set->height, ref_set->levels, cur_set->width, cur_set->height, cur_set->levels);
+    if (max_level >= ref_set->levels)
+        return fail(SVO_ERR_ARG, "svo_klt_track: max_level %d, the sets hold %d levels", max_level, ref_set->levels);
+    for (int32_t p = 0; p < n_pairs; ++p)
+        if (frames[2 * p] < 0 || frames[2 * p] >= ref_set->n_frames || frames[2 * p + 1] < 0 ||
+            frames[2 * p + 1] >= cur_set->n_frames)
+            return fail(SVO_ERR_ARG, "svo_klt_track: pair %d: frame index out of range", p);
+    if (median_disparity)
+        for (int32_t p = 0; p < n_pairs; ++p) median_disparity[p] = std::nan("");
+    if (n_pairs == 0 || n == 0) return SVO_OK;
+    SVO_HIP(hipSetDevice(c->device));
+    SVO_HIP(set_join(ref_set));
+    SVO_HIP(set_join(cur_set));
+    hipStream_t s = ctx_stream(c);
+    const size_t P = (size_t)n_pairs, N = (size_t)n, TR = trace ? N * (size_t)(max_level + 1) * 8 : 0;
+    Carve cv;
+    const size_t o_off = cv.take((P + 1) * 4), o_fr = cv.take(P * 8), o_rpx = cv.take(N * 16), o_cpx = cv.take(N * 16),
+                 o_st = cv.take(N), o_tr = cv.take(TR);
+    void* base = nullptr;
+    hipError_t e = ctx_scratch(c, cv.total, &base);
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, "svo_klt_track scratch: %s", hipGetErrorString(e));
+    char* db = static_cast<char*>(base);
+    struct Piece { size_t off; const void* src; size_t bytes; };
+    const Piece in[] = {{o_off, feat_off, (P + 1) * 4}, {o_fr, frames, P * 8}, {o_rpx, ref_px, N * 16}, {o_cpx, cur_px, N * 16}};
+    for (const Piece& pc : in)
+        if (e == hipSuccess) e = stage_copy(c, db + pc.off, pc.src, pc.bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) {
+        svo::KltArgs a{};
+        a.ref_base = ref_set->d_base;
+        a.cur_base = cur_set->d_base;
+        a.ref_stride = ref_set->stride;
+        a.cur_stride = cur_set->stride;
+        a.feat_off = reinterpret_cast<int32_t*>(db + o_off);
+        a.frames = reinterpret_cast<int32_t*>(db + o_fr);
+        a.ref_px = reinterpret_cast<double*>(db + o_rpx);
+        a.cur_px = reinterpret_cast<double*>(db + o_cpx);
+        a.status = reinterpret_cast<uint8_t*>(db + o_st);
+        a.trace = trace ? reinterpret_cast<int32_t*>(db + o_tr) : nullptr;
+        a.n = (int32_t)n;
+        a.n_pairs = n_pairs;
+        a.win = win;
+        a.max_level = max_level;
+        a.max_iterations = max_iterations;
+        a.epsilon = epsilon;
+        a.min_eig = min_eig_threshold;
+        a.geom = ref_set->geom;
+        svo::launch_klt(a, s);
+        e = hipGetLastError();
+    }
+    struct Out { size_t off; void* dst; size_t bytes; };
+    const Out out[] = {{o_cpx, cur_px, N * 16}, {o_st, status, N}, {o_tr, trace, TR}};
+    for (const Out& o : out)
+        if (e == hipSuccess) e = stage_copy(c, o.dst, db + o.off, o.bytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, "svo_klt_track: %s", hipGetErrorString(e));
+    if (median_disparity) {  // src/algorithm.cpp:64-79: float32 differences, double norm, computeMedian
+        std::vector<double> disp;
+        for (int32_t p = 0; p < n_pairs; ++p) {
+            disp.clear();
+            for (int64_t k = feat_off[p]; k < feat_off[p + 1]; ++k) {
+                if (!status[k]) continue;
+                const double dx = (double)((float)ref_px[2 * k] - (float)cur_px[2 * k]);
+                const double dy = (double)((float)ref_px[2 * k + 1] - (float)cur_px[2 * k + 1]);
+                disp.push_back(std::sqrt(dx * dx + dy * dy));
+            }
+            median_disparity[p] = svo::two_view_median(disp.data(), (int64_t)disp.size());
+        }
+    }
+    return SVO_OK;
+}
+
 }  // extern "C"

@@ -255,6 +255,22 @@ struct BundleAdjustArgs {  // windowed bundle adjustment over a batch of problem
 void launch_ba_structure(const BundleAdjustArgs& a, hipStream_t s);
 void launch_ba_joint(const BundleAdjustArgs& a, hipStream_t s);
 
+struct KltArgs {  // pyramidal Lucas-Kanade over a batch of frame pairs (klt.hip; contract: include/svo_c.h)
+    const uint8_t* ref_base;   // intensity stack of frame 0 of the ref set; frame f is ref_stride bytes further
+    const uint8_t* cur_base;
+    int64_t ref_stride, cur_stride;
+    const int32_t* frames;     // [n_pairs][2]
+    const int32_t* feat_off;   // [n_pairs + 1]
+    const double* ref_px;      // [n][2]
+    double* cur_px;            // [n][2] in/out
+    uint8_t* status;           // [n]
+    int32_t* trace;            // [n][max_level + 1][2] or nullptr
+    int32_t n, n_pairs, win, max_level, max_iterations;
+    double epsilon, min_eig;
+    LevelGeom geom;
+};
+void launch_klt(const KltArgs& a, hipStream_t s);
+
 // FeatureSelection (feature_select.hip)
 int feature_detect_segments(int64_t npx);
 void launch_feature_detect(const uint8_t* plane, int width, int height, int thr, int* seg_counts, uint32_t* keys,

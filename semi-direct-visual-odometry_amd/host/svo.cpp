@@ -585,6 +585,34 @@ TwoViewResult initializeTwoView(Context& ctx, std::shared_ptr<Frame>& refFrame, 
     return res;
 }
 
+// ------------------------------------------------------------------ sparse optical flow
+bool algorithm::computeOpticalFlowSparse(Context& ctx, std::shared_ptr<Frame>& refFrame, std::shared_ptr<Frame>& curFrame,
+                                         uint32_t patchSize, double disparityThreshold) {
+    const std::size_t n = refFrame->numberObservation();
+    const std::size_t cap = n ? n : 1;
+    std::vector<double> refPx(2 * cap), curPx(2 * cap);
+    for (std::size_t i = 0; i < n; ++i)
+        for (int j = 0; j < 2; ++j) refPx[2 * i + j] = curPx[2 * i + j] = refFrame->m_features[i]->m_pixelPosition[j];
+    std::vector<uint8_t> status(cap, 0);
+    const int32_t off[2] = {0, (int32_t)n}, frames[2] = {0, 0};
+    double medianDisparity = 0.0;
+    check(svo_klt_track(ctx.get(), refFrame->m_imagePyramid.set(), curFrame->m_imagePyramid.set(), 1, frames, off,
+                        refPx.data(), curPx.data(), (int32_t)patchSize, 3, 30, 1e-4, 1e-4, status.data(), nullptr,
+                        &medianDisparity));
+    for (std::size_t i = 0; i < n; ++i)
+        if (status[i]) {  // (:68-73)
+            auto feature = std::make_shared<Feature>(curFrame.get(), Vec2{curPx[2 * i], curPx[2 * i + 1]});
+            feature->m_gradientMagnitude = 0.0;
+            curFrame->m_features.push_back(feature);
+        }
+    if (medianDisparity < disparityThreshold) return false;  // (:81-84)
+    std::size_t cnt = 0;
+    refFrame->m_features.erase(std::remove_if(refFrame->m_features.begin(), refFrame->m_features.end(),
+                                              [&](const auto& feature) { return !(feature != nullptr && status[cnt++] == 1); }),
+                               refFrame->m_features.end());
+    return true;
+}
+
 // ------------------------------------------------------------------ trajectory / feature dump
 namespace utils {
 void writeInFile(const Pose& refAbsPose, std::ostream& w) {

@@ -257,6 +257,13 @@ namespace algorithm {
 // the frames' current poses
 void triangulate3DWorldPoints(Context& ctx, const std::shared_ptr<Frame>& refFrame,
                               const std::shared_ptr<Frame>& curFrame, std::vector<Vec3>& pointsWorld);
+// computeOpticalFlowSparse (src/algorithm.cpp:29-107, called src/system.cpp:128-129) over svo_klt_track (window
+// patchSize, 4 levels, 30 iterations, eps 1e-4, initial flow = the ref positions): one Feature(curFrame, px, 0.0, 0.0,
+// 0) appended to curFrame per tracked point, in order; false when the median disparity is below the threshold (the
+// cur features stay, refFrame is untouched); otherwise the untracked features are erased from refFrame (order kept).
+// Nothing tracked: the median is NaN, which is not below the threshold (true), as in the reference.
+bool computeOpticalFlowSparse(Context& ctx, std::shared_ptr<Frame>& refFrame, std::shared_ptr<Frame>& curFrame,
+                              uint32_t patchSize, double disparityThreshold);
 }  // namespace algorithm
 struct TwoViewResult {
     bool ok = false;             // recoverPose found a hypothesis with matches in front of both cameras

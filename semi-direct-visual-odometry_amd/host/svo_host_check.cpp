@@ -35,6 +35,10 @@
 //                                  and to its point in edge order, the first n_key frames the keyframes; prints with
 //                                  %a "chi init final removed", per frame "pose p[7]" and "left n", per point
 //                                  "pt X Y Z type observations"
+//   svo_host_check klt IMAGES.raw W H PX.bin N WIN THR   algorithm::computeOpticalFlowSparse (GPU); IMAGES.raw: the
+//                                  ref then the cur image (W x H bytes each); PX.bin: N x px[2] doubles, the ref
+//                                  frame's features; prints "klt result n_ref n_cur", then with %a "ref x y" per
+//                                  feature left in the ref frame and "cur x y" per feature of the cur frame
 #include <algorithm>
 #include <array>
 #include <chrono>
@@ -208,6 +212,30 @@ int main(int argc, char** argv) {
                 std::vector<Vec3> tri;
                 algorithm::triangulate3DWorldPoints(ctx, ref, cur, tri);
                 for (const Vec3& x : tri) std::printf("tri %.17g %.17g %.17g\n", x[0], x[1], x[2]);
+            }
+            return 0;
+        }
+        if (mode == "klt" && argc >= 9) {
+            const int w = std::atoi(argv[3]), h = std::atoi(argv[4]), n = std::atoi(argv[6]), win = std::atoi(argv[7]);
+            const double thr = std::atof(argv[8]);
+            const std::vector<uint8_t> imgs = read_raw(argv[2], 2 * (size_t)w * h);
+            std::vector<double> px(2 * (size_t)n);
+            std::ifstream f(argv[5], std::ios::binary);
+            f.read(reinterpret_cast<char*>(px.data()), (std::streamsize)(px.size() * sizeof(double)));
+            if (!f) throw std::runtime_error("short pixel file");
+            Context ctx(0);
+            auto cam = std::make_shared<PinholeCamera>(PinholeCamera{w, h, 150.0, 150.0, w / 2.0, h / 2.0});
+            auto ref = std::make_shared<Frame>(ctx, cam, imgs.data(), 4);
+            auto cur = std::make_shared<Frame>(ctx, cam, imgs.data() + (size_t)w * h, 4);
+            for (int i = 0; i < n; ++i)
+                ref->m_features.push_back(std::make_shared<Feature>(ref.get(), Vec2{px[2 * i], px[2 * i + 1]}));
+            const bool ok = algorithm::computeOpticalFlowSparse(ctx, ref, cur, (uint32_t)win, thr);
+            std::printf("klt %d %zu %zu\n", ok ? 1 : 0, ref->numberObservation(), cur->numberObservation());
+            for (const auto& ft : ref->m_features) std::printf("ref %a %a\n", ft->m_pixelPosition[0], ft->m_pixelPosition[1]);
+            for (const auto& ft : cur->m_features) {
+                if (ft->m_frame != cur.get() || ft->m_gradientMagnitude != 0.0 || ft->m_gradientOrientation != 0.0 || ft->m_point)
+                    throw std::runtime_error("cur feature is not Feature(cur, px, 0.0, 0.0, 0)");
+                std::printf("cur %a %a\n", ft->m_pixelPosition[0], ft->m_pixelPosition[1]);
             }
             return 0;
         }

@@ -504,6 +504,77 @@ int svo_klt_track(svo_ctx* ctx, const svo_pyramid_set* ref_set, const svo_pyrami
                   int32_t max_level, int32_t max_iterations, double epsilon, double min_eig_threshold, uint8_t* status,
                   int32_t* trace, double* median_disparity);
 
+/* ---------------------------------------------------------------- essential-matrix RANSAC
+ * Replaces algorithm::computeEssentialMatrix's cv::findEssentialMat(ref, cur, K, RANSAC, 0.999, 1.0, status)
+ * (src/algorithm.cpp:109-171, called src/system.cpp:137) for n_pairs independent frame pairs.  OpenCV is not part of
+ * the reference tree; the arithmetic below is THIS PROJECT'S CONTRACT, modelled on findEssentialMat (five-point minimal
+ * solver, Sampson distance on normalised coordinates, threshold over the mean focal length, confidence-driven sample
+ * count, the best minimal model returned without refinement) and NOT pinned to OpenCV's samples or bits.
+ * The convention is the one svo_two_view_init consumes: cur^T E ref = 0, E = [t]x R for X_cur = R X_ref + t.
+ * Matches are laid out by feat_off as for svo_triangulate_dlt: pair p owns matches feat_off[p] .. feat_off[p+1]-1.
+ *
+ * svo_essential_score: the inliers of given models.
+ *   hyp_off   n_pairs + 1: pair p owns models hyp_off[p] .. hyp_off[p+1]-1 of E_hyp (m x 9, row-major)
+ *   counts    m: the inliers of each model among its pair's matches
+ *   mask      NULL, or n (uint8): per pair the inlier mask of its first model with the strictly largest count (a count
+ *             of 0 never wins: the mask is then 0)
+ * Per match: both pixels are rounded to float32 and widened (the reference's static_cast<float>), x = (u - cx) / fx,
+ * y = (v - cy) / fy.  With x1 = ref, x2 = cur and every product and sum one rounded IEEE operation in the written order
+ *   a_i = (E_i0 x1.x + E_i1 x1.y) + E_i2                 (i = 0, 1, 2)
+ *   b_j = (E_0j x2.x + E_1j x2.y) + E_2j                 (j = 0, 1)
+ *   num = (x2.x a_0 + x2.y a_1) + a_2
+ *   den = ((a_0 a_0 + a_1 a_1) + b_0 b_0) + b_1 b_1
+ *   err = (num num) / den
+ * and the match is an inlier iff err <= thr2, thr = threshold / ((fx + fy) / 2), thr2 = thr thr (a NaN never is).
+ *
+ * svo_essential_ransac:
+ *   ref_px, cur_px  n x 2, not modified;  threshold in pixels (the reference passes 1.0), confidence (0.999),
+ *   max_iterations (1000; 1 .. SVO_ESSENTIAL_MAX_ITERATIONS), seed
+ *   E           n_pairs x 9 row-major, Frobenius norm 1 (its sign is unspecified)
+ *   mask        n (uint8): the winner's inliers;  n_inliers  n_pairs: their number
+ *   iterations  n_pairs: samples consumed;  best  n_pairs x 2: the winner's sample h and its solution index k
+ *   status      n_pairs: 0 ok; -1 fewer than 5 matches or no sample produced a model with an inlier: E and mask are 0,
+ *               best is -1
+ *   hyp_E, hyp_count  both NULL, or the trace: n_pairs x max_iterations x 10 x 9 models and n_pairs x max_iterations
+ *               x 10 counts (-1: the sample has no such solution; -2: a sample past `iterations`, its models 0)
+ * Per pair p with n_p matches:
+ *   1 sampling, integer only.  mix(z): z += 0x9E3779B97F4A7C15; z = (z ^ z>>30) * 0xBF58476D1CE4E5B9;
+ *     z = (z ^ z>>27) * 0x94D049BB133111EB; return z ^ z>>31 (64-bit, the splitmix64 finaliser).  Draw c = 0 .. 255 of
+ *     sample h is r = mix(seed ^ (p << 44) ^ (h << 8) ^ c), index ((r >> 32) * n_p) >> 32; a draw equal to an index
+ *     already held is skipped; the first five distinct indices are the sample; a sample without five by c = 255 has no
+ *     models.
+ *   2 five-point solver.  The models of a sample are the real solutions of Nister's system: E in the four-dimensional
+ *     null space of the five epipolar equations x2^T E x1 = 0 on the normalised points, E = x X + y Y + z Z + W,
+ *     with det E = 0 and E E^T E - tr(E E^T) E / 2 = 0 (ten cubics in x, y, z).  How the null space and the starting
+ *     roots are found is not part of the contract (here: Householder QR, Gauss-Jordan of the 10 x 20 system, the roots
+ *     of det B(z) by simultaneous Ehrlich-Aberth iteration).  Every starting root is polished by Gauss-Newton on the
+ *     ten cubics in (x, y, z), for as long as the scaled residual |c| / |E|_F^3 decreases and at most 10 steps; a root
+ *     whose polished scaled residual exceeds 1e-9 is discarded, as is one whose unit model lies within 1e-6 (largest
+ *     entry difference, up to sign) of one already kept.  The models are scaled to Frobenius norm 1; their order
+ *     within a sample is unspecified.
+ *   3 every model is scored with the arithmetic of svo_essential_score.
+ *   4 stopping rule, sequential in definition: best = 0, niters = max_iterations; for h = 0, 1, .. while h < niters:
+ *     a model of sample h with a strictly larger count than best becomes the winner (k ascending); after sample h, if
+ *     best rose, niters = update(confidence, (n_p - best) / n_p, max_iterations), evaluated in double with std::log
+ *     and std::pow: num = max(1 - confidence, DBL_MIN), den = 1 - (1 - ep)^5; den < DBL_MIN: 0; log den >= 0 or
+ *     -log num >= max_iterations (-log den): max_iterations; otherwise rint(log num / log den).
+ *     `iterations` is the h at which the loop ends.  Samples are computed in rounds; the result does not depend on
+ *     the rounds.
+ *   5 mask = the winner's inliers, n_inliers their count, E the winner.
+ * Every count is an integer sum; there are no floating-point atomics: equal inputs give equal bytes.
+ * SVO_ERR_ARG: threshold <= 0, confidence outside (0, 1), max_iterations outside 1 .. 65536, feat_off not ascending
+ * (all of these before the context is looked at), more than 65535 pairs in one svo_essential_ransac call, a null
+ * argument, one of hyp_E / hyp_count without the other.
+ * Synchronous; waits for pending alignment chains. */
+#define SVO_ESSENTIAL_MAX_ITERATIONS 65536
+int svo_essential_score(svo_ctx* ctx, const svo_camera* cam, int32_t n_pairs, const int32_t* feat_off,
+                        const int32_t* hyp_off, const double* E_hyp, const double* ref_px, const double* cur_px,
+                        double threshold, int32_t* counts, uint8_t* mask);
+int svo_essential_ransac(svo_ctx* ctx, const svo_camera* cam, int32_t n_pairs, const int32_t* feat_off,
+                         const double* ref_px, const double* cur_px, double threshold, double confidence,
+                         int32_t max_iterations, uint64_t seed, double* E, uint8_t* mask, int32_t* n_inliers,
+                         int32_t* iterations, int32_t* best, int32_t* status, double* hyp_E, int32_t* hyp_count);
+
 #ifdef __cplusplus
 }
 #endif

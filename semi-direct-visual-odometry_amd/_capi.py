@@ -111,6 +111,11 @@ _SIGNATURES = [
                                     c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("svo_klt_track", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                 c_int32, c_int32, c_double, c_double, c_void_p, c_void_p, c_void_p]),
+    ("svo_essential_score", c_int32, [c_void_p, ctypes.POINTER(SvoCamera), c_int32, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_double, c_void_p, c_void_p]),
+    ("svo_essential_ransac", c_int32, [c_void_p, ctypes.POINTER(SvoCamera), c_int32, c_void_p, c_void_p, c_void_p,
+                                       c_double, c_double, c_int32, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p]),
 ]
 
 EXPORTED = [s[0] for s in _SIGNATURES]

@@ -1448,3 +1448,80 @@ def compute_optical_flow_sparse(ref_frame, cur_frame, patch_size, disparity_thre
         return False
     ref_frame.features = [f for f, t in zip(ref_frame.features, tracked) if t]
     return True
+
+
+# ---------------------------------------------------------------- essential-matrix RANSAC
+class EssentialResult:
+    """E (P, 3, 3), mask (n,) uint8, n_inliers / iterations / status (P,), best (P, 2); with trace=True also hyp_E
+    (P, max_iterations, 10, 3, 3) and hyp_count (P, max_iterations, 10)."""
+
+
+def essential_score_batch(camera, feat_off, hyp_off, E_hyp, ref_px, cur_px, threshold=1.0, want_mask=True, ctx=None):
+    """svo_essential_score over arrays: the inlier count of every model of E_hyp (pair p owns models
+    hyp_off[p]:hyp_off[p+1]) among its pair's matches, and per pair the mask of its first model with the strictly
+    largest count.  Returns (counts (m,) int32, mask (n,) uint8 or None)."""
+    ctx = ctx or default_context()
+    feat_off = np.ascontiguousarray(feat_off, np.int32)
+    hyp_off = np.ascontiguousarray(hyp_off, np.int32)
+    P = len(feat_off) - 1
+    if len(hyp_off) != P + 1:
+        raise ValueError("hyp_off and feat_off differ in length")
+    n, m = int(feat_off[-1]), int(hyp_off[-1])
+    E_hyp = np.ascontiguousarray(E_hyp, np.float64).reshape(m, 9)
+    ref_px = np.ascontiguousarray(ref_px, np.float64).reshape(n, 2)
+    cur_px = np.ascontiguousarray(cur_px, np.float64).reshape(n, 2)
+    counts = np.zeros(m, np.int32)
+    mask = np.zeros(n, np.uint8) if want_mask else None
+    cam = camera.as_c()
+    check(lib().svo_essential_score(ctx.handle, ctypes.byref(cam), P, ptr(feat_off), ptr(hyp_off), ptr(E_hyp),
+                                    ptr(ref_px), ptr(cur_px), float(threshold), ptr(counts), ptr(mask)))
+    return counts, mask
+
+
+def essential_ransac_batch(camera, feat_off, ref_px, cur_px, threshold=1.0, confidence=0.999, max_iterations=1000,
+                           seed=0, trace=False, ctx=None):
+    """svo_essential_ransac over arrays (the cv::findEssentialMat of algorithm::computeEssentialMatrix,
+    src/algorithm.cpp:130, for a batch of pairs; include/svo_c.h states the contract).  Pair p owns matches
+    feat_off[p]:feat_off[p+1] of ref_px / cur_px ((n, 2), not modified)."""
+    ctx = ctx or default_context()
+    feat_off = np.ascontiguousarray(feat_off, np.int32)
+    P = len(feat_off) - 1
+    n = int(feat_off[-1]) if P >= 0 else 0
+    ref_px = np.ascontiguousarray(ref_px, np.float64).reshape(n, 2)
+    cur_px = np.ascontiguousarray(cur_px, np.float64).reshape(n, 2)
+    r = EssentialResult()
+    r.E = np.zeros((P, 3, 3))
+    r.mask = np.zeros(n, np.uint8)
+    r.n_inliers = np.zeros(P, np.int32)
+    r.iterations = np.zeros(P, np.int32)
+    r.best = np.zeros((P, 2), np.int32)
+    r.status = np.zeros(P, np.int32)
+    mi = max(int(max_iterations), 0)
+    r.hyp_E = np.zeros((P, mi, 10, 3, 3)) if trace else None
+    r.hyp_count = np.zeros((P, mi, 10), np.int32) if trace else None
+    cam = camera.as_c()
+    check(lib().svo_essential_ransac(ctx.handle, ctypes.byref(cam), P, ptr(feat_off), ptr(ref_px), ptr(cur_px),
+                                     float(threshold), float(confidence), int(max_iterations),
+                                     int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(r.E), ptr(r.mask), ptr(r.n_inliers),
+                                     ptr(r.iterations), ptr(r.best), ptr(r.status), ptr(r.hyp_E), ptr(r.hyp_count)))
+    return r
+
+
+def compute_essential_matrix(ref_frame, cur_frame, repro_error, threshold_corresponding_points, seed=0, ctx=None):
+    """algorithm::computeEssentialMatrix(refFrame, curFrame, reproError, thresholdCorrespondingPoints, E)
+    (src/algorithm.cpp:109-171): feature i of ref_frame matches feature i of cur_frame; the RANSAC (confidence 0.999,
+    threshold repro_error px, at most 1000 samples) runs on the device, the matches it rejects are erased from both
+    frames (order kept), and the result is (ok, E): ok when both frames keep more than the threshold.  A pair without
+    a model keeps no feature and returns a zero E."""
+    n = ref_frame.number_observation()
+    if cur_frame.number_observation() != n:
+        raise ValueError("the frames differ in their number of features")
+    ref_px = np.array(ref_frame.feature_arrays()[0], np.float64).reshape(n, 2)
+    cur_px = np.array(cur_frame.feature_arrays()[0], np.float64).reshape(n, 2)
+    r = essential_ransac_batch(ref_frame.camera, [0, n], ref_px, cur_px, float(repro_error), 0.999, 1000, seed, ctx=ctx)
+    keep = r.mask == 1
+    for fr in (ref_frame, cur_frame):  # one assignment per frame: one bump of its cached feature arrays
+        fr.features = [f for f, k in zip(fr.features, keep) if k]
+    ok = (ref_frame.number_observation() > threshold_corresponding_points and
+          cur_frame.number_observation() > threshold_corresponding_points)
+    return ok, r.E[0].copy()

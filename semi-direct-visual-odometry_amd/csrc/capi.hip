@@ -1974,4 +1974,248 @@ int svo_klt_track(svo_ctx* c, const svo_pyramid_set* ref_set, const svo_pyramid_
     return SVO_OK;
 }
 
+// ------------------------------------------------------------------ essential-matrix RANSAC
+static int essential_scalars(const char* fn, double threshold) {
+    if (!(threshold > 0.0) || !std::isfinite(threshold)) return fail(SVO_ERR_ARG, "%s: threshold must be positive and finite", fn);
+    return SVO_OK;
+}
+// thr^2 on normalised coordinates: the pixel threshold over the mean focal length, squared
+static double essential_thr2(const svo_camera* cam, double threshold) {
+    const double thr = threshold / ((cam->fx + cam->fy) / 2.0);
+    return thr * thr;
+}
+static void essential_camera(svo::EssentialArgs& a, const svo_camera* cam, double threshold) {
+    a.fx = cam->fx;
+    a.fy = cam->fy;
+    a.cx = cam->cx;
+    a.cy = cam->cy;
+    a.thr2 = essential_thr2(cam, threshold);
+}
+
+int svo_essential_score(svo_ctx* c, const svo_camera* cam, int32_t n_pairs, const int32_t* feat_off,
+                        const int32_t* hyp_off, const double* E_hyp, const double* ref_px, const double* cur_px,
+                        double threshold, int32_t* counts, uint8_t* mask) {
+    if (int r = essential_scalars("svo_essential_score", threshold)) return r;
+    int64_t n = 0, m = 0;
+    if (int r = two_view_check("svo_essential_score", n_pairs, feat_off, &n)) return r;
+    if (int r = two_view_check("svo_essential_score (hyp_off)", n_pairs, hyp_off, &m)) return r;
+    if (!c || !cam || (n > 0 && (!ref_px || !cur_px)) || (m > 0 && (!E_hyp || !counts)))
+        return fail(SVO_ERR_ARG, "svo_essential_score: null argument");
+    if (mask && n > 0) std::memset(mask, 0, (size_t)n);
+    if (n_pairs == 0 || m == 0) return SVO_OK;
+    SVO_HIP(hipSetDevice(c->device));
+    hipStream_t s = ctx_stream(c);
+    const size_t P = (size_t)n_pairs, N = (size_t)n, M = (size_t)m;
+    Carve cv;
+    const size_t o_off = cv.take((P + 1) * 4), o_hoff = cv.take((P + 1) * 4), o_rpx = cv.take(N * 16),
+                 o_cpx = cv.take(N * 16), o_xn = cv.take(N * 32), o_E = cv.take(M * 72), o_cnt = cv.take(M * 4),
+                 o_best = cv.take(P * 72), o_has = cv.take(P * 4), o_mask = cv.take(N);
+    void* base = nullptr;
+    hipError_t e = ctx_scratch(c, cv.total, &base);
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, "svo_essential_score scratch: %s", hipGetErrorString(e));
+    char* db = static_cast<char*>(base);
+    struct Piece { size_t off; const void* src; size_t bytes; };
+    const Piece in[] = {{o_off, feat_off, (P + 1) * 4}, {o_hoff, hyp_off, (P + 1) * 4}, {o_rpx, ref_px, N * 16},
+                        {o_cpx, cur_px, N * 16}, {o_E, E_hyp, M * 72}};
+    for (const Piece& pc : in)
+        if (e == hipSuccess) e = stage_copy(c, db + pc.off, pc.src, pc.bytes, hipMemcpyHostToDevice, s);
+    svo::EssentialArgs a{};
+    essential_camera(a, cam, threshold);
+    a.feat_off = reinterpret_cast<int32_t*>(db + o_off);
+    a.hyp_off = reinterpret_cast<int32_t*>(db + o_hoff);
+    a.ref_px = reinterpret_cast<double*>(db + o_rpx);
+    a.cur_px = reinterpret_cast<double*>(db + o_cpx);
+    a.xn = reinterpret_cast<double*>(db + o_xn);
+    a.hyp_E = reinterpret_cast<double*>(db + o_E);
+    a.counts = reinterpret_cast<int32_t*>(db + o_cnt);
+    a.best_E = reinterpret_cast<double*>(db + o_best);
+    a.has_best = reinterpret_cast<int32_t*>(db + o_has);
+    a.mask = reinterpret_cast<uint8_t*>(db + o_mask);
+    a.n = (int32_t)n;
+    a.n_pairs = n_pairs;
+    a.n_models = (int32_t)m;
+    if (e == hipSuccess) {
+        svo::launch_essential_normalise(a, s);
+        svo::launch_essential_score_models(a, s);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = stage_copy(c, counts, db + o_cnt, M * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess && mask && n > 0) {  // per pair: its first model with the strictly largest count
+        std::vector<double> best(P * 9, 0.0);
+        std::vector<int32_t> has(P, 0);
+        for (int32_t p = 0; p < n_pairs; ++p) {
+            int32_t top = 0;
+            for (int32_t k = hyp_off[p]; k < hyp_off[p + 1]; ++k)
+                if (counts[k] > top) {
+                    top = counts[k];
+                    has[p] = 1;
+                    std::memcpy(&best[(size_t)p * 9], E_hyp + (size_t)k * 9, 72);
+                }
+        }
+        e = stage_copy(c, db + o_best, best.data(), P * 72, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = stage_copy(c, db + o_has, has.data(), P * 4, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) {
+            svo::launch_essential_mask(a, s);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = stage_copy(c, mask, db + o_mask, N, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);  // (also keeps `best` and `has` alive for the copies)
+    }
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, "svo_essential_score: %s", hipGetErrorString(e));
+    return SVO_OK;
+}
+
+int svo_essential_ransac(svo_ctx* c, const svo_camera* cam, int32_t n_pairs, const int32_t* feat_off,
+                         const double* ref_px, const double* cur_px, double threshold, double confidence,
+                         int32_t max_iterations, uint64_t seed, double* E, uint8_t* mask, int32_t* n_inliers,
+                         int32_t* iterations, int32_t* best, int32_t* status, double* hyp_E, int32_t* hyp_count) {
+    // the scalar parameters and the layout first: these need no context
+    if (int r = essential_scalars("svo_essential_ransac", threshold)) return r;
+    if (!(confidence > 0.0 && confidence < 1.0)) return fail(SVO_ERR_ARG, "svo_essential_ransac: confidence must lie in (0, 1)");
+    if (max_iterations < 1 || max_iterations > SVO_ESSENTIAL_MAX_ITERATIONS)
+        return fail(SVO_ERR_ARG, "svo_essential_ransac: max_iterations %d outside 1..%d", max_iterations, SVO_ESSENTIAL_MAX_ITERATIONS);
+    int64_t n = 0;
+    if (int r = two_view_check("svo_essential_ransac", n_pairs, feat_off, &n)) return r;
+    if (n_pairs > 65535) return fail(SVO_ERR_ARG, "svo_essential_ransac: more than 65535 pairs in one call");
+    if (!c || !cam || (n_pairs > 0 && (!E || !n_inliers || !iterations || !best || !status)) ||
+        (n > 0 && (!ref_px || !cur_px || !mask)) || ((hyp_E != nullptr) != (hyp_count != nullptr)))
+        return fail(SVO_ERR_ARG, "svo_essential_ransac: null argument");
+    if (n_pairs == 0) return SVO_OK;
+    const size_t P = (size_t)n_pairs, N = (size_t)n, MI = (size_t)max_iterations;
+    const bool trace = hyp_E != nullptr;
+    std::fill(E, E + P * 9, 0.0);
+    if (n > 0) std::memset(mask, 0, N);
+    std::fill(best, best + 2 * P, -1);
+    if (trace) {
+        std::fill(hyp_E, hyp_E + P * MI * 90, 0.0);
+        std::fill(hyp_count, hyp_count + P * MI * 10, -2);
+    }
+    std::vector<int32_t> active(P), niters(P, max_iterations), top(P, 0), select(P), has(P, 0);
+    bool any = false;
+    for (size_t p = 0; p < P; ++p) {
+        const int32_t np = feat_off[p + 1] - feat_off[p];
+        active[p] = np >= 5;
+        any = any || active[p];
+        n_inliers[p] = 0;
+        iterations[p] = 0;
+        status[p] = -1;
+    }
+    if (!any) return SVO_OK;
+    SVO_HIP(hipSetDevice(c->device));
+    hipStream_t s = ctx_stream(c);
+    // samples per round: the rounds only bound the work past the stop, the result does not depend on them
+    const int32_t chunk = std::min<int32_t>((max_iterations + 63) / 64 * 64, n_pairs >= 64 ? 64 : 256);
+    const size_t CH = (size_t)chunk;
+    Carve cv;
+    const size_t o_off = cv.take((P + 1) * 4), o_rpx = cv.take(N * 16), o_cpx = cv.take(N * 16), o_xn = cv.take(N * 32),
+                 o_act = cv.take(P * 4), o_nsol = cv.take(P * CH * 4), o_E = cv.take(P * CH * 720),
+                 o_cnt = cv.take(P * CH * 40), o_sel = cv.take(P * 4), o_best = cv.take(P * 72), o_has = cv.take(P * 4),
+                 o_mask = cv.take(N);
+    void* base = nullptr;
+    hipError_t e = ctx_scratch(c, cv.total, &base);
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, "svo_essential_ransac scratch: %s", hipGetErrorString(e));
+    char* db = static_cast<char*>(base);
+    struct Piece { size_t off; const void* src; size_t bytes; };
+    const Piece in[] = {{o_off, feat_off, (P + 1) * 4}, {o_rpx, ref_px, N * 16}, {o_cpx, cur_px, N * 16}};
+    for (const Piece& pc : in)
+        if (e == hipSuccess) e = stage_copy(c, db + pc.off, pc.src, pc.bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(db + o_best, 0, P * 72, s);
+    svo::EssentialArgs a{};
+    essential_camera(a, cam, threshold);
+    a.feat_off = reinterpret_cast<int32_t*>(db + o_off);
+    a.ref_px = reinterpret_cast<double*>(db + o_rpx);
+    a.cur_px = reinterpret_cast<double*>(db + o_cpx);
+    a.xn = reinterpret_cast<double*>(db + o_xn);
+    a.active = reinterpret_cast<int32_t*>(db + o_act);
+    a.nsol = reinterpret_cast<int32_t*>(db + o_nsol);
+    a.hyp_E = reinterpret_cast<double*>(db + o_E);
+    a.counts = reinterpret_cast<int32_t*>(db + o_cnt);
+    a.select = reinterpret_cast<int32_t*>(db + o_sel);
+    a.best_E = reinterpret_cast<double*>(db + o_best);
+    a.has_best = reinterpret_cast<int32_t*>(db + o_has);
+    a.mask = reinterpret_cast<uint8_t*>(db + o_mask);
+    a.seed = seed;
+    a.n = (int32_t)n;
+    a.n_pairs = n_pairs;
+    a.chunk = chunk;
+    a.max_iterations = max_iterations;
+    if (e == hipSuccess) {
+        svo::launch_essential_normalise(a, s);
+        e = hipGetLastError();
+    }
+    std::vector<int32_t> cnt(P * CH * 10);
+    std::vector<double> round_E(trace ? P * CH * 90 : 0);
+    for (int32_t h0 = 0; any && e == hipSuccess; h0 += chunk) {
+        a.h0 = h0;
+        e = stage_copy(c, db + o_act, active.data(), P * 4, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) {
+            svo::launch_essential_solve(a, s);
+            svo::launch_essential_score_samples(a, s);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = stage_copy(c, cnt.data(), db + o_cnt, P * CH * 40, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && trace) e = stage_copy(c, round_E.data(), db + o_E, P * CH * 720, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) break;
+        // the sequential stopping rule on this round's counts
+        any = false;
+        bool rose_any = false;
+        for (size_t p = 0; p < P; ++p) {
+            select[p] = -1;
+            if (!active[p]) continue;
+            const int32_t np = feat_off[p + 1] - feat_off[p];
+            int32_t h = h0;
+            for (; h < h0 + chunk && h < niters[p]; ++h) {
+                const size_t slot = p * CH + (size_t)(h - h0);
+                bool rose = false;
+                for (int k = 0; k < 10; ++k) {
+                    const int32_t v = cnt[slot * 10 + k];
+                    if (trace) hyp_count[(p * MI + (size_t)h) * 10 + k] = v;
+                    if (v > top[p]) {
+                        top[p] = v;
+                        best[2 * p] = h;
+                        best[2 * p + 1] = k;
+                        select[p] = (int32_t)(slot * 10 + k);
+                        rose = true;
+                    }
+                }
+                if (trace) std::memcpy(hyp_E + (p * MI + (size_t)h) * 90, &round_E[slot * 90], 720);
+                if (rose)
+                    niters[p] = svo::essential_update_iterations(confidence, (double)(np - top[p]) / (double)np, max_iterations);
+            }
+            if (h >= niters[p]) {
+                active[p] = 0;
+                iterations[p] = h;
+            } else {
+                any = true;
+            }
+            rose_any = rose_any || select[p] >= 0;
+        }
+        if (rose_any) {
+            e = stage_copy(c, db + o_sel, select.data(), P * 4, hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) {
+                svo::launch_essential_gather(a, s);
+                e = hipGetLastError();
+            }
+            if (e == hipSuccess) e = hipStreamSynchronize(s);  // `select` is rewritten by the next round
+        }
+    }
+    for (size_t p = 0; p < P; ++p) {
+        has[p] = top[p] > 0;
+        status[p] = has[p] ? 0 : -1;
+        n_inliers[p] = top[p];
+    }
+    if (e == hipSuccess) e = stage_copy(c, db + o_has, has.data(), P * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && n > 0) {
+        svo::launch_essential_mask(a, s);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = stage_copy(c, E, db + o_best, P * 72, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = stage_copy(c, mask, db + o_mask, N, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, "svo_essential_ransac: %s", hipGetErrorString(e));
+    return SVO_OK;
+}
+
 }  // extern "C"

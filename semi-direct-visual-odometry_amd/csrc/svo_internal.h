@@ -271,6 +271,33 @@ struct KltArgs {  // pyramidal Lucas-Kanade over a batch of frame pairs (klt.hip
 };
 void launch_klt(const KltArgs& a, hipStream_t s);
 
+struct EssentialArgs {  // essential-matrix RANSAC over a batch of frame pairs (essential.hip; contract: include/svo_c.h)
+    const int32_t* feat_off;   // [n_pairs + 1]
+    const double* ref_px;      // [n][2]
+    const double* cur_px;      // [n][2]
+    double* xn;                // [n][4] normalised ref.x ref.y cur.x cur.y (normalise)
+    const int32_t* active;     // [n_pairs] solve / score_samples: pairs still sampling; nullptr: all
+    int32_t* nsol;             // [n_pairs][chunk] models of each sample of the chunk; -1: the sample drew no five
+    double* hyp_E;             // solve / score_samples: [n_pairs][chunk][10][9]; score_models: [n_models][9]
+    const int32_t* hyp_off;    // score_models: [n_pairs + 1]
+    int32_t* counts;           // [n_pairs][chunk][10] (-1: no such model) or [n_models]
+    const int32_t* select;     // gather: [n_pairs] index of a model in hyp_E, -1: keep
+    double* best_E;            // [n_pairs][9]
+    const int32_t* has_best;   // mask: [n_pairs]
+    uint8_t* mask;             // [n]
+    uint64_t seed;
+    double fx, fy, cx, cy, thr2;
+    int32_t n, n_pairs, n_models, h0, chunk, max_iterations;
+};
+void launch_essential_normalise(const EssentialArgs& a, hipStream_t s);
+void launch_essential_solve(const EssentialArgs& a, hipStream_t s);
+void launch_essential_score_samples(const EssentialArgs& a, hipStream_t s);
+void launch_essential_score_models(const EssentialArgs& a, hipStream_t s);
+void launch_essential_gather(const EssentialArgs& a, hipStream_t s);
+void launch_essential_mask(const EssentialArgs& a, hipStream_t s);
+// OpenCV's RANSACUpdateNumIters: the sample count that reaches `confidence` at outlier ratio `ep` (host, double)
+int essential_update_iterations(double confidence, double ep, int max_iterations);
+
 // FeatureSelection (feature_select.hip)
 int feature_detect_segments(int64_t npx);
 void launch_feature_detect(const uint8_t* plane, int width, int height, int thr, int* seg_counts, uint32_t* keys,

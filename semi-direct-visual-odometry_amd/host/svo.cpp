@@ -613,6 +613,29 @@ bool algorithm::computeOpticalFlowSparse(Context& ctx, std::shared_ptr<Frame>& r
     return true;
 }
 
+// ------------------------------------------------------------------ essential-matrix RANSAC
+bool algorithm::computeEssentialMatrix(Context& ctx, std::shared_ptr<Frame>& refFrame, std::shared_ptr<Frame>& curFrame,
+                                       double reproError, uint32_t thresholdCorrespondingPoints, std::array<double, 9>& E,
+                                       uint64_t seed) {
+    std::vector<double> refPx, curPx;
+    matched_pixels(*refFrame, *curFrame, refPx, curPx);
+    const int32_t n = (int32_t)refFrame->numberObservation();
+    const int32_t off[2] = {0, n};
+    const svo_camera cam = refFrame->m_camera->c();
+    std::vector<uint8_t> status(n ? (std::size_t)n : 1, 0);
+    int32_t nInliers = 0, iterations = 0, best[2] = {-1, -1}, code = 0;
+    check(svo_essential_ransac(ctx.get(), &cam, 1, off, refPx.data(), curPx.data(), reproError, 0.999, 1000, seed,
+                               E.data(), status.data(), &nInliers, &iterations, best, &code, nullptr, nullptr));
+    for (auto* frame : {&refFrame, &curFrame}) {  // (:140-161) the rejected matches leave both frames, order kept
+        std::size_t cnt = 0;
+        auto& features = (*frame)->m_features;
+        features.erase(std::remove_if(features.begin(), features.end(), [&](const auto&) { return status[cnt++] == 0; }),
+                       features.end());
+    }
+    return refFrame->numberObservation() > thresholdCorrespondingPoints &&
+           curFrame->numberObservation() > thresholdCorrespondingPoints;  // (:166-170)
+}
+
 // ------------------------------------------------------------------ trajectory / feature dump
 namespace utils {
 void writeInFile(const Pose& refAbsPose, std::ostream& w) {

@@ -264,6 +264,13 @@ void triangulate3DWorldPoints(Context& ctx, const std::shared_ptr<Frame>& refFra
 // Nothing tracked: the median is NaN, which is not below the threshold (true), as in the reference.
 bool computeOpticalFlowSparse(Context& ctx, std::shared_ptr<Frame>& refFrame, std::shared_ptr<Frame>& curFrame,
                               uint32_t patchSize, double disparityThreshold);
+// computeEssentialMatrix (src/algorithm.cpp:109-171, called src/system.cpp:137) over svo_essential_ransac (threshold
+// reproError px, confidence 0.999, at most 1000 samples): feature i of refFrame matches feature i of curFrame; the
+// matches the RANSAC rejects are erased from both frames (order kept); true when both keep more than the threshold.
+// E is row-major with Frobenius norm 1 (zero when no model was found: every feature leaves).
+bool computeEssentialMatrix(Context& ctx, std::shared_ptr<Frame>& refFrame, std::shared_ptr<Frame>& curFrame,
+                            double reproError, uint32_t thresholdCorrespondingPoints, std::array<double, 9>& E,
+                            uint64_t seed = 0);
 }  // namespace algorithm
 struct TwoViewResult {
     bool ok = false;             // recoverPose found a hypothesis with matches in front of both cameras

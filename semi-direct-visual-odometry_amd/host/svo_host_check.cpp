@@ -239,6 +239,42 @@ int main(int argc, char** argv) {
             }
             return 0;
         }
+        if (mode == "essential" && argc >= 3) {
+            // DATA.bin (doubles): fx fy cx cy w h reproError threshold seed n, then n x (ref.x ref.y cur.x cur.y)
+            std::ifstream f(argv[2], std::ios::binary);
+            f.seekg(0, std::ios::end);
+            const size_t bytes = (size_t)f.tellg();
+            f.seekg(0);
+            std::vector<double> v(bytes / sizeof(double));
+            f.read(reinterpret_cast<char*>(v.data()), (std::streamsize)bytes);
+            size_t q = 0;
+            auto take = [&]() { return v.at(q++); };
+            const double fx = take(), fy = take(), cx = take(), cy = take();
+            const int w = (int)take(), h = (int)take();
+            const double reproError = take();
+            const uint32_t threshold = (uint32_t)take();
+            const uint64_t seed = (uint64_t)take();
+            const int n = (int)take();
+            Context ctx(0);
+            auto cam = std::make_shared<PinholeCamera>(PinholeCamera{w, h, fx, fy, cx, cy});
+            const std::vector<uint8_t> img((size_t)w * h, 0);
+            auto ref = std::make_shared<Frame>(ctx, cam, img.data(), 1);
+            auto cur = std::make_shared<Frame>(ctx, cam, img.data(), 1);
+            for (int i = 0; i < n; ++i) {
+                const double rx = take(), ry = take(), ux = take(), uy = take();
+                ref->m_features.push_back(std::make_shared<Feature>(ref.get(), Vec2{rx, ry}));
+                cur->m_features.push_back(std::make_shared<Feature>(cur.get(), Vec2{ux, uy}));
+            }
+            std::array<double, 9> E{};
+            const bool ok = algorithm::computeEssentialMatrix(ctx, ref, cur, reproError, threshold, E, seed);
+            std::printf("essential %d %zu %zu\n", ok ? 1 : 0, ref->numberObservation(), cur->numberObservation());
+            std::printf("E");
+            for (double x : E) std::printf(" %a", x);
+            std::printf("\n");
+            for (const auto& ft : ref->m_features) std::printf("ref %a %a\n", ft->m_pixelPosition[0], ft->m_pixelPosition[1]);
+            for (const auto& ft : cur->m_features) std::printf("cur %a %a\n", ft->m_pixelPosition[0], ft->m_pixelPosition[1]);
+            return 0;
+        }
         if (mode == "wba" && argc >= 3) {
             std::ifstream f(argv[2], std::ios::binary);
             f.seekg(0, std::ios::end);
@@ -435,7 +471,7 @@ int main(int argc, char** argv) {
             if (reps > 0) std::printf("ms %.6f\n", total_ms / reps);
             return 0;
         }
-        std::fprintf(stderr, "usage: svo_host_check io | fs W H CELL THR NUM BUCKET IMAGE [EX EY]... | fv W H CELL THR IMAGE | init DATA.bin | wba DATA.bin\n");
+        std::fprintf(stderr, "usage: svo_host_check io | fs W H CELL THR NUM BUCKET IMAGE [EX EY]... | fv W H CELL THR IMAGE | init DATA.bin | essential DATA.bin | wba DATA.bin\n");
         return 2;
     } catch (const std::exception& e) {
         std::fprintf(stderr, "svo_host_check: %s\n", e.what());

@@ -28,8 +28,10 @@
 //      vec[nth - 1] need; the sources write the mailbox (LDS, slot k - 1), EXEC set to the row's side mask;  barrier
 //   3. the kept side's targets take the mailbox values (EXEC-masked moves into the rows); all read the next
 //      pivot's candidates.
-// A mailbox larger than the layout's kMbCap swaps runs in chunks.  Segments of <= 1024 (LayC: 512) continue on wave 0 in
-// its rows 0..15 (0..7) without barriers; the depth limit falls back to the restated heap select (adversarial inputs only).
+// A mailbox larger than the layout's kMbCap swaps runs in chunks.  LayA moves a segment of <= 7168 positions (kMid) to
+// LDS once and runs its rounds there on all eight waves (the mid-size phase).  Segments of <= 2048 (LayC: 512)
+// continue on wave 0 in its rows 0..31 (0..7) without barriers; the depth limit falls back to the restated heap select
+// (adversarial inputs only).
 // No global traffic but the two reads of K1's residuals per pair and level (one per pass).
 #include "svo_internal.h"
 #include "svo_math.h"
@@ -51,9 +53,10 @@ using namespace refsel;
 
 constexpr int kVT = 512;              // threads per pair
 constexpr int kVW = kVT / 64;         // waves
-// segments of <= OW positions (a layout's one-wave size, a multiple of 256: 1024 for LayA / LayB, 512 for LayC, whose
-// mailbox holds no more) continue on wave 0 (its rows 0 .. OW / 64 - 1); wave 0's register rows for the MAD pass are staged by the other waves during its one-wave rounds
-// past the one-wave segment and its mailbox (mbx[2 OW, ...))
+// segments of <= OW positions (a layout's one-wave size, a multiple of 256: 2048 for the product's LayA / LayB, 1024 in
+// the debug kernel's copies of them, 512 for LayC, whose mailbox holds no more) continue on wave 0
+// (its rows 0 .. OW / 64 - 1); wave 0's register rows for the MAD pass are staged by the other waves during its
+// one-wave rounds past the one-wave segment and its mailbox (mbx[2 OW, ...))
 #ifndef SVO_ONEWAVE
 #define SVO_ONEWAVE 2048
 #endif
@@ -64,7 +67,7 @@ constexpr int kRowPad = 128;          // record planes: rows padded to two group
 // A register layout: G the data registers (refv_rows.h: rows 0 .. G::kRegRows - 1 above G::kBase), R rows in all
 // (the rest in LDS), a mailbox of MB doubles (Ks beyond it exchanges in chunks), PRE: the MAD pass's rows load
 // during the median pass's one-wave rounds (staged in the mailbox).
-template <class G, int R, uint32_t MB, bool PRE, uint32_t OW>
+template <class G, int R, uint32_t MB, bool PRE, uint32_t OW, uint32_t MID = 0>
 struct Lay {
     using Rows = G;
     static constexpr int kRows = R;
@@ -74,6 +77,17 @@ struct Lay {
     static constexpr uint32_t kCap = (uint32_t)R * kVT;
     static constexpr uint32_t kOneWave = OW;
     static constexpr uint32_t kStage = 2 * OW;
+    // mid-size rounds (0: none): a segment of OW < S <= MID positions moves to mbx[0, MID) once and its rounds run there
+    // on all eight waves, with the mailbox behind it (mbx[MID, MB): Ks <= S / 2 swaps, so no round of it is chunked)
+    static constexpr uint32_t kMid = MID;
+    // rows per batch of the mid-size walks: the debug kernel's copy of a layout (OW 1024) has no registers to spare
+    // below its fence for more than one row in flight
+#ifndef SVO_MID_BATCH
+#define SVO_MID_BATCH 4
+#endif
+    static constexpr int kMidBatch = OW >= 2048 ? SVO_MID_BATCH : 1;
+    static_assert(MID == 0 || (MID % kVT == 0 && MID > OW && MID / kVT <= 64 && MID + MID / 2 <= MB),
+                  "mid-size segment and its mailbox inside the mailbox array");
     static_assert(OW % 256 == 0 && OW / 64 <= G::kRegRows && OW <= 4096, "one-wave rows: register quads of wave 0");
     static_assert(R > G::kRegRows && R <= kRowPad, "rows");
     static_assert(2 * OW <= MB && MB % 64 == 0, "one-wave segment and its mailbox");
@@ -84,7 +98,11 @@ struct Lay {
 #ifndef SVO_ONEWAVE_A
 #define SVO_ONEWAVE_A SVO_ONEWAVE
 #endif
-using LayA = Lay<RowsA, 98, 12288, true, SVO_ONEWAVE_A>;   // 50 176 slots: 88 register rows (v80..v255) + 10 LDS rows
+// SVO_MID: the mid-size cap of the layouts that have the phase (-DSVO_MID=0: none, the kernel without the phase)
+#ifndef SVO_MID
+#define SVO_MID 7168
+#endif
+using LayA = Lay<RowsA, 98, 12288, true, SVO_ONEWAVE_A, SVO_MID>;   // 50 176 slots: 88 register rows (v80..v255) + 10 LDS rows
 using LayB = Lay<RowsB, 118, 4352, false, SVO_ONEWAVE>;  // 60 416 slots: 92 register rows (v72..v255) + 26 LDS rows
 // 65 536 slots (2621 features at patch 5): 96 register rows (v64..v255) + 32 LDS rows; the LDS rows leave a 1344-swap
 // mailbox (163 032 of the CU's 163 840 LDS bytes in all), so the large rounds exchange in chunks, each walking only its
@@ -93,7 +111,7 @@ using LayC = Lay<RowsC, 128, 1344, false, 512>;
 // the debug kernel (svo_debug_robust_scale: round traces, diagnostics) runs LayA / LayB with 1024-position one-wave
 // rounds: its diagnostics need registers that the 2048-position one-wave code leaves below neither fence (v80 / v72).
 // Both sizes run the same introselect rounds; only the point where wave 0 takes the segment over differs
-using LayADbg = Lay<RowsA, 98, 12288, true, 1024>;
+using LayADbg = Lay<RowsA, 98, 12288, true, 1024, SVO_MID>;
 using LayBDbg = Lay<RowsB, 118, 4352, false, 1024>;
 
 template <class L>
@@ -114,7 +132,7 @@ struct VShared {
 static_assert(sizeof(VShared<LayC>) <= 163840, "LayC's shared state fits the CU's LDS");
 
 struct VDiag {  // svo_debug_robust_scale diagnostics
-    uint32_t nblock[2], nwave[2], heap[2], nchunk[2];
+    uint32_t nblock[2], nwave[2], heap[2], nchunk[2];  // (nblock: block rounds | mid-size rounds << 16)
     uint64_t cyc[2];
     uint64_t ph[12];  // thread 0's cycles per phase, both passes: load, classify, barrier 1, publish + side
                       // ranks, sources, barrier 2, targets, exits (dump, one-wave rounds, final), scan, crossing,
@@ -203,6 +221,9 @@ struct VSel {
     static constexpr uint32_t kMbCap = L::kMbCap;
     static constexpr uint32_t kOneWave = L::kOneWave;
     static constexpr uint32_t kStage = L::kStage;
+    static constexpr uint32_t kMid = L::kMid;
+    static constexpr int kMidRows = (int)(kMid / kVT);  // rows of 512 positions of the mid-size segment
+    static constexpr int kMidBatch = L::kMidBatch;      // its rows per range-tested batch (their loads in flight together)
     static constexpr int kQuads = (R + 3) / 4;  // quads of rows the block rounds walk (kGenQuads of them in registers)
     // below this many rows a wave classifies and exchanges row by row (indexed registers) instead of walking the quads
 #ifndef SVO_FEWROWS
@@ -236,6 +257,7 @@ struct VSel {
     double lo_val;
     int P;
     bool small_round = false;  // (stamps build: the current block round has < 2048 positions)
+    uint32_t moff = 0, mlen = 0;  // mid-size phase: the segment's first position and length at its dump (f, l, nth are relative to moff inside the phase)
 #if defined(SVO_STAMPS) && defined(SVO_STAMPS_WAVES)
     uint32_t phacc[12] = {};  // (stamps build, per wave: cycles per phase of this pass so far)
 #endif
@@ -333,9 +355,10 @@ struct VSel {
         return low_mask((uint32_t)(hi < 0 ? 0 : hi)) & ~low_mask((uint32_t)(lo < 0 ? 0 : lo));
     }
     // the owner of position q stores its current value in pub[slot]
+    template <bool kM = false>
     __device__ __forceinline__ void publish(uint32_t q, int slot) {
         if (((q >> 6) & (kVW - 1)) != (uint32_t)wave) return;
-        const double x = row_val((int)(q >> 9));
+        const double x = kM ? sh.mbx[(q & ~(uint32_t)(kVT - 1)) + (uint32_t)tid] : row_val((int)(q >> 9));
         if ((uint32_t)lane == (q & 63u)) sh.pub[slot] = x;
     }
     // positions [f, l) -> dst[q - dbase]; the other lanes store to dummy + lane (branch-free)
@@ -586,9 +609,10 @@ struct VSel {
     }
     // candidate q of the next round (slot i): its owner publishes the pre-value and, if q is one of this round's
     // swap targets (side: 0 GE ranked from the left, 1 LE ranked from the right, rank <= ks), its rank
+    template <bool kM = false>
     __device__ __forceinline__ void publish_cand(const Ctl& C, uint32_t q, int i, uint32_t ks, int side) {
         if (((q >> 6) & (kVW - 1)) != (uint32_t)wave) return;
-        const double x = row_val((int)(q >> 9));
+        const double x = kM ? sh.mbx[(q & ~(uint32_t)(kVT - 1)) + (uint32_t)tid] : row_val((int)(q >> 9));
         uint32_t k = 0;
         if (ks) {
             const uint32_t s = q >> 6, b = q & 63u, r = s >> 3;
@@ -696,7 +720,14 @@ struct VSel {
         constexpr int r0 = 4 * kQG * Gq, r1 = r0 + 4 * (int)sizeof...(Is) - 1;
         if (r1 < ra || r0 > rb) return;
         if (r0 >= ra && r1 <= rb) {  // whole group inside
-            if constexpr (!kWrite && G::kTgt8 && kQG == 4 && sizeof...(Is) == 4 && r1 < 4 * kGenQuads) {
+#if defined(SVO_STAMPS)
+            // (stamps build: four reads in flight; with the mid-size phase the debug kernel's clock reads leave the
+            // eight-read block's 24 temporaries no room below the fence)
+            constexpr bool kUse8 = false;
+#else
+            constexpr bool kUse8 = G::kTgt8;
+#endif
+            if constexpr (!kWrite && kUse8 && kQG == 4 && sizeof...(Is) == 4 && r1 < 4 * kGenQuads) {
                 G::template tgt8<2 * Gq, S>(p, pb[r0 >> 6]);  // (eight mailbox reads in flight per block)
                 G::template tgt8<2 * Gq + 1, S>(p, pb[r0 >> 6]);
             } else {
@@ -742,6 +773,95 @@ struct VSel {
         xk1 = k1;
         if (side == 0) ex_quads<kWrite, 0>(C, p, ra, rb, k0);
         else ex_quads<kWrite, 1>(C, p, ra, rb, k0);
+    }
+
+    // ------------------------------------------------------------------ mid-size rounds: classify and exchange from LDS
+    // A segment of kOneWave < S <= kMid positions lives in A = mbx[0, kMid) (A[i]: position moff + i; f, l, nth are
+    // relative to moff during the phase) with the position map of the block rounds on the relative positions: i in
+    // lane i % 64 of wave (i / 64) % 8, row i / 512, so thread t owns A[512 j + t] and every access to A inside a round
+    // is its owner's.  The records, counts, scan and searches are the block round's own; the rows are plain LDS loads
+    // with compile-time row numbers (no register indexing, the rows' loads in flight together), and a row's masks
+    // stay in lane j of four accumulators from the classification to the exchange.
+    __device__ __forceinline__ void classify_mid(double p, uint32_t ch, double x0, uint32_t (&acc)[4]) {
+        double* const A = sh.mbx;
+        // std::iter_swap(first, chosen) of __move_median_to_first, by the owners (who read the rows below themselves)
+        if ((f & (uint32_t)(kVT - 1)) == (uint32_t)tid) A[f] = p;
+        if ((ch & (uint32_t)(kVT - 1)) == (uint32_t)tid) A[ch] = x0;
+        const WaveRows w = wave_segment(f >> 6, (l - 1) >> 6);
+        const int r0 = (int)(f >> 9), r1 = (int)((l - 1) >> 9);
+        acc[0] = acc[1] = acc[2] = acc[3] = 0;  // lane j: row j's GE lo, GE hi, LE lo, LE hi
+        // rows in batches of kMidBatch: one range test per batch, the batch's loads in flight together (a row of the
+        // batch outside [r0, r1] is compared too: its index stays inside A, and its lanes are masked below)
+#pragma unroll
+        for (int g = 0; g < (kMidRows + kMidBatch - 1) / kMidBatch; ++g) {
+            if (kMidBatch * g + kMidBatch - 1 < r0 || kMidBatch * g > r1) continue;
+            double x[kMidBatch];
+#pragma unroll
+            for (int i = 0; i < kMidBatch; ++i)
+                if (kMidBatch * g + i < kMidRows) x[i] = A[kVT * (kMidBatch * g + i) + tid];
+#pragma unroll
+            for (int i = 0; i < kMidBatch; ++i) {
+                const int j = kMidBatch * g + i;
+                if (j >= kMidRows) continue;
+                const uint64_t ge = __ballot(!(x[i] < p)), le = __ballot(!(p < x[i]));
+                acc[0] = lane_write(acc[0], (uint32_t)ge, (uint32_t)j);
+                acc[1] = lane_write(acc[1], (uint32_t)(ge >> 32), (uint32_t)j);
+                acc[2] = lane_write(acc[2], (uint32_t)le, (uint32_t)j);
+                acc[3] = lane_write(acc[3], (uint32_t)(le >> 32), (uint32_t)j);
+            }
+        }
+        // this wave's steps inside [f, l) (GE without the pivot at f), as in classify()
+        const int j = lane;
+        const bool in = j >= w.rlo && j <= w.rhi;
+        uint64_t gm = in ? ~0ull : 0ull, lm = gm;
+        if (j == w.rlo) { gm &= w.ge_first; lm &= w.le_first; }
+        if (j == w.rhi) { gm &= w.last; lm &= w.last; }
+        acc[0] &= (uint32_t)gm;
+        acc[1] &= (uint32_t)(gm >> 32);
+        acc[2] &= (uint32_t)lm;
+        acc[3] &= (uint32_t)(lm >> 32);
+        // (rows 64..127 of the planes were zeroed at the phase's entry)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) sh.rec[c][wave][j] = acc[c];
+        sh.cnt[wave][j] = (__popc(acc[0]) + __popc(acc[1])) | ((__popc(acc[2]) + __popc(acc[3])) << 16);
+    }
+    // side 0: GE ranked from the left, side 1: LE ranked from the right, rows ra..rb; ranks k <= ks: kWrite stores the
+    // value in the mailbox slot k - 1, else the position takes it (generic_row's arithmetic on the accumulators' masks)
+    template <bool kWrite>
+    __device__ __forceinline__ void exchange_mid(const Ctl& C, const uint32_t (&acc)[4], int side, uint32_t ks, int ra,
+                                                 int rb) {
+        double* const A = sh.mbx;
+        double* const mb = sh.mbx + kMid;
+        const uint32_t dslot = kMbCap - kMid + (uint32_t)lane;  // mbx[kMbCap + lane]
+        const uint32_t ml = side == 0 ? acc[0] : acc[2], mh = side == 0 ? acc[1] : acc[3];
+        // rows in batches of kMidBatch, one range test per batch.  A row of the batch outside [ra, rb] is harmless: the
+        // range only skips rows that hold no rank <= ks of this side, and a lane without one goes to the dummy slot
+#pragma unroll
+        for (int g = 0; g < (kMidRows + kMidBatch - 1) / kMidBatch; ++g) {
+            if (kMidBatch * g + kMidBatch - 1 < ra || kMidBatch * g > rb) continue;
+            uint32_t a[kMidBatch];
+            uint64_t okm[kMidBatch];
+            double t[kMidBatch];
+#pragma unroll
+            for (int i = 0; i < kMidBatch; ++i) {
+                const int j = kMidBatch * g + i;
+                if (j >= kMidRows) continue;
+                const uint64_t m = ((uint64_t)uni(lane_read(mh, j)) << 32) | uni(lane_read(ml, j));
+                const uint32_t pp = uni(lane_read(C.pw[0], j));
+                const uint32_t b = side == 0 ? (pp & 0xFFFFu) : C.totL - 1u - (pp >> 16);
+                const uint32_t kk = side == 0 ? b + lanes_below(m) : b - lanes_below(m);
+                okm[i] = m & __ballot(kk < ks);
+                a[i] = lane_sel(okm[i], kk, dslot);
+                t[i] = kWrite ? A[kVT * j + tid] : mb[a[i]];
+            }
+#pragma unroll
+            for (int i = 0; i < kMidBatch; ++i) {
+                const int j = kMidBatch * g + i;
+                if (j >= kMidRows) continue;
+                if (kWrite) mb[a[i]] = t[i];
+                else if ((okm[i] >> lane) & 1ull) A[kVT * j + tid] = t[i];
+            }
+        }
     }
 
     // ------------------------------------------------------------------ one block round
@@ -790,6 +910,23 @@ struct VSel {
         if (tracing() && tid == 0) ++dg->ntr;
         __syncthreads();
     }
+    // a mid-size round's record (kind 2): absolute positions in the header, the phase's segment in the vector slots
+    __device__ __forceinline__ void trace_mid(uint32_t f0, uint32_t l0, double p, uint32_t ks, uint32_t tg, uint32_t tl,
+                                              uint32_t cut) {
+        double* const v = trace_rec(2, moff + f0, moff + l0, p, ks, tg, tl, moff + cut);
+        if (v) {
+#pragma unroll
+            for (int j = 0; j < kMidRows; ++j) {
+                const uint32_t i = (uint32_t)(kVT * j + tid);
+                if (i < mlen) v[moff + i] = sh.mbx[i];
+            }
+        }
+        __syncthreads();
+        if (tracing() && tid == 0) ++dg->ntr;
+        __syncthreads();
+    }
+    // kM: a mid-size round (the segment in LDS, see classify_mid): the same round on relative positions
+    template <bool kM = false>
     __device__ __forceinline__ void block_round(double p, uint32_t ch, double x0, double (&cand)[4]) {
         refresh_ids();
         uint64_t tstamp = dg ? clock64() : 0;
@@ -798,7 +935,9 @@ struct VSel {
         const uint32_t S0 = l - f;
         small_round = S0 < 2048;
 #endif
-        classify(p, ch, x0);
+        [[maybe_unused]] uint32_t macc[4];
+        if constexpr (kM) classify_mid(p, ch, x0, macc);
+        else classify(p, ch, x0);
         VSTAMP(1);
         __syncthreads();
         VSTAMP(2);
@@ -879,7 +1018,7 @@ struct VSel {
         const uint32_t nf = right ? cut : f, nl = right ? l : cut;
         // vec[nth - 1] after this round (never touched again): only L_{Ks} can sit at cut - 1
         const bool record = cut == nth && !rec;
-        if (record) publish(lk == cut - 1u ? rk : cut - 1u, 4);
+        if (record) publish<kM>(lk == cut - 1u ? rk : cut - 1u, 4);
         const uint32_t nS = nl - nf;
         const bool need = nS > kOneWave && depth > 0;  // another block round follows
         const uint32_t cq[4] = {nf + 1u, nf + nS / 2u, nl - 1u, nf};
@@ -887,13 +1026,14 @@ struct VSel {
         const int src_side = right ? 0 : 1, tgt_side = right ? 1 : 0;
         if (need) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) publish_cand(C, cq[i], i, ks, tgt_side);
+            for (int i = 0; i < 4; ++i) publish_cand<kM>(C, cq[i], i, ks, tgt_side);
         }
         const uint32_t sl = (l - 1) >> 6;
         const uint32_t s0L = f >> 6, s1L = lk != kNone ? lk >> 6 : 0u;       // L_k, k <= Ks (boundary: s1L)
         const uint32_t s0R = rk != kNone ? rk >> 6 : sl + 1u, s1R = sl;       // R_k, k <= Ks (boundary: s0R)
         // Ks beyond the mailbox: chunks of kMbCap ranks, the masks from the records (see exchange).
-        const uint32_t nch = ks == 0 ? 1u : (ks + kMbCap - 1u) / kMbCap;
+        // (a mid-size round: Ks <= S / 2 <= its mailbox, one chunk)
+        const uint32_t nch = kM || ks == 0 ? 1u : (ks + kMbCap - 1u) / kMbCap;
         uint32_t ck[4] = {0, 0, 0, 0};  // the candidates' target ranks (0: not a target)
         VSTAMP(3);
         // a chunk's steps on one side: the positions of its ranks (k0, k1] (side 0: GE ranked from the left, L_k;
@@ -910,7 +1050,12 @@ struct VSel {
         };
         for (uint32_t it = 0; it < nch; ++it) {
             const uint32_t k0 = it * kMbCap, k1 = ks < k0 + kMbCap ? ks : k0 + kMbCap;
-            if (ks) {
+            if constexpr (kM) {
+                if (ks) {
+                    if (src_side == 0) exchange_mid<true>(C, macc, 0, ks, (int)(f >> 9), (int)(lk >> 9));
+                    else exchange_mid<true>(C, macc, 1, ks, (int)(rk >> 9), (int)((l - 1) >> 9));
+                }
+            } else if (ks) {
                 if (kChunkSteps && nch > 1) {
                     uint32_t c0, c1;
                     chunk_steps(src_side, k0, k1, c0, c1);
@@ -935,7 +1080,17 @@ struct VSel {
                     }
                 }
             }
-            if (ks) {
+            if constexpr (kM) {
+                if (ks) {
+                    if (tgt_side == 0) exchange_mid<false>(C, macc, 0, ks, (int)(f >> 9), (int)(lk >> 9));
+                    else exchange_mid<false>(C, macc, 1, ks, (int)(rk >> 9), (int)((l - 1) >> 9));
+                    if (need) {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+                            if (ck[i] > 0) cand[i] = uni(sh.mbx[kMid + ck[i] - 1u]);
+                    }
+                }
+            } else if (ks) {
                 if (kChunkSteps && nch > 1) {
                     uint32_t c0, c1;
                     chunk_steps(tgt_side, k0, k1, c0, c1);
@@ -959,7 +1114,7 @@ struct VSel {
         if (dg && tid == 0) dg->nchunk[P] += nch > 1 ? 1u : 0u;
 #if defined(SVO_STAMPS) && !defined(SVO_STAMPS_WAVES)
         if (kStampOn && dg && tid == 0 && dg->nlog < 64) {
-            dg->log[dg->nlog][0] = S0;
+            dg->log[dg->nlog][0] = S0 | (kM ? 0x80000000u : 0u);  // (bit 31: a mid-size round)
             dg->log[dg->nlog][1] = (uint32_t)(clock64() - tround);
             ++dg->nlog;
         }
@@ -968,7 +1123,8 @@ struct VSel {
             const uint32_t f0 = f, l0 = l;
             f = nf;
             l = nl;
-            trace_block(f0, l0, p, ks, totG, totL, cut);
+            if constexpr (kM) trace_mid(f0, l0, p, ks, totG, totL, cut);
+            else trace_block(f0, l0, p, ks, totG, totL, cut);
         }
         f = nf;
         l = nl;
@@ -1198,7 +1354,9 @@ struct VSel {
             }
         }
         uint32_t nblock = 0;
-        while (l - f > kOneWave && depth > 0) {
+        // block rounds down to the mid-size cap (without the phase: down to the one-wave size)
+        constexpr uint32_t kBlockMin = kMid > 0 ? kMid : kOneWave;
+        while (l - f > kBlockMin && depth > 0) {
             --depth;
             ++nblock;
             uint32_t ch;
@@ -1208,8 +1366,55 @@ struct VSel {
         }
         tstamp = dg ? clock64() : 0;
         __syncthreads();  // the last round's targets still read the mailbox the exits overwrite
+        // ---- the mid-size phase: kOneWave < S <= kMid, rounds left.  Every value that steers it (f, l, depth, the
+        // pivots, and inside a round Ks and the ranks) is block-uniform: f, l and the ranks come from sh.srch, the
+        // candidates from sh.pub / the mailbox, all read by all eight waves after a barrier, and depth counts the same
+        // rounds in every wave.  So all waves take the phase or none, run the same number of rounds, and meet at the
+        // same barriers; no wave leaves on a value of its own.
+        bool in_mid = false;
+        if constexpr (kMid > 0) in_mid = l - f > kOneWave && depth > 0;  // (then S <= kMid by the loop above)
+        uint32_t nmid = 0;
+        if (in_mid) {
+            moff = f;
+            mlen = l - f;
+            dump(sh.mbx, moff, sh.mbx + kMbCap);  // the data registers and LDS rows are dead from here on
+            // rows 64..127 of the record planes: no step of the phase (the block rounds wrote them)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) sh.rec[c][wave][64 + lane] = 0;
+            sh.cnt[wave][64 + lane] = 0;
+            f = 0;
+            l = mlen;
+            nth -= moff;
+            __syncthreads();
+            while (l - f > kOneWave && depth > 0) {
+                --depth;
+                ++nmid;
+                uint32_t ch;
+                double p;
+                median3(cand[0], cand[1], cand[2], f + 1u, f + (l - f) / 2u, l - 1u, ch, p);
+                block_round<true>(uni(p), uni(ch), cand[3], cand);
+            }
+            __syncthreads();  // the last round's targets have written their positions
+            if (l - f > kOneWave) {  // depth limit: the segment to the global scratch for the heap select
+                for (uint32_t i = f + (uint32_t)tid; i < l; i += kVT) gseg[moff + i] = sh.mbx[i];
+            } else {  // the segment to mbx[0, S): the one-wave rounds' input
+                constexpr int kN = (int)(kOneWave / kVT);
+                double t[kN];
+#pragma unroll
+                for (int j = 0; j < kN; ++j) {
+                    const uint32_t i = f + (uint32_t)(kVT * j + tid);
+                    t[j] = sh.mbx[i < kMid ? i : 0u];
+                }
+                __syncthreads();
+#pragma unroll
+                for (int j = 0; j < kN; ++j) sh.mbx[kVT * j + tid] = t[j];
+            }
+            f += moff;
+            l += moff;
+            nth += moff;
+        }
         if (l - f > kOneWave) {  // depth limit on a large segment: heap select in the pair's global scratch
-            dump(gseg, 0, gseg + gdummy);
+            if (!in_mid) dump(gseg, 0, gseg + gdummy);
             __threadfence_block();
             __syncthreads();
             if (tid == 0) {
@@ -1221,7 +1426,7 @@ struct VSel {
         } else {
             double* const seg = sh.mbx;  // positions f0 + i
             const uint32_t f0 = f;
-            dump(seg, f0, sh.mbx + kMbCap);
+            if (!in_mid) dump(seg, f0, sh.mbx + kMbCap);
             __syncthreads();
 #if !defined(SVO_K2V_KEEP_WAVES)
             if (retire && !preload_next && wave != 0) {  // (not in the debug kernel: kRetire false)
@@ -1271,7 +1476,7 @@ struct VSel {
         }
 #endif
         if (dg && tid == 0) {
-            dg->nblock[P] = nblock;
+            dg->nblock[P] = nblock | (nmid << 16);  // (mid-size rounds in the high half)
             dg->cyc[P] = clock64() - t0;
         }
     }

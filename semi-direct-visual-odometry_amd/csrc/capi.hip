@@ -859,9 +859,9 @@ static int run_batch(svo_align_batch* b, hipEvent_t* marks) {
     if (marks || b->n_pairs < kSplitMin || one_chain) {
         svo::launch_align(a, ctx_stream(c), marks);
     } else {
-        // two independent half-batch chains on two streams: one chain's latency-bound stages (the
-        // per-pair robust scale) overlap the other chain's feature stages.  Results are per pair and
-        // independent of the split.
+        // independent sub-batch chains, one stream each (two, or four for the reference-mode K2V path at
+        // >= kSplitsRefvMin pairs; SVO_CHAINS overrides): one chain's latency-bound stages (the per-pair robust
+        // scale) overlap the other chains' feature stages.  Results are per pair and independent of the split.
         static const int env_chains = getenv("SVO_CHAINS") ? atoi(getenv("SVO_CHAINS")) : 0;  // (measurement knobs,
         static const int env_stagger = getenv("SVO_STAGGER") ? atoi(getenv("SVO_STAGGER")) : -1;  //  read once)
         const bool k2v = svo::scale_impl() != SVO_SCALE_K2R && (int64_t)a.max_slots <= svo::refv_max_slots();

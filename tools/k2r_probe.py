@@ -47,8 +47,9 @@ if plain:
 if impl == svo_amd.SCALE_K2V:
     for p in range(2):
         cyc, nb, nl, hp, ch = out[2 + 5 * p: 7 + 5 * p]
-        print(f"K2V pass {p}: {cyc:.0f} cycles, block rounds {nb:.0f}, one-wave rounds {nl:.0f}, heap select {hp:.0f}, "
-              f"chunked exchanges {ch:.0f}")
+        nb, nm = int(nb) & 0xFFFF, int(nb) >> 16  # (mid-size rounds in the counter's high half)
+        print(f"K2V pass {p}: {cyc:.0f} cycles, block rounds {nb}, mid-size rounds {nm}, one-wave rounds {nl:.0f}, "
+              f"heap select {hp:.0f}, chunked exchanges {ch:.0f}")
     names = ("load", "classify", "barrier1", "publish+ranks", "sources", "barrier2", "targets", "exits", "scan",
              "crossing", "searches")
     print("K2V cycles per phase (thread 0, both passes): " + ", ".join(f"{a} {x:.0f}" for a, x in zip(names, out[12:23])))
@@ -60,7 +61,10 @@ if impl == svo_amd.SCALE_K2V:
             print(f"  w{w}  " + " ".join(f"{x:9.0f}" for x in pw[w, :11]))
     else:
         log = out[24:152].reshape(-1, 2)
-        print("K2V block rounds (S, cycles; stamps build):", [tuple(int(x) for x in r) for r in log if r[0] >= 0])
+        rs = [(int(r[0]), int(r[1])) for r in log if r[0] >= 0]
+        print("K2V block rounds (S, cycles; stamps build):", [r for r in rs if r[0] < 1 << 31])
+        mid = [(S - (1 << 31), c) for S, c in rs if S >= 1 << 31]  # (bit 31 of S marks a mid-size round)
+        print(f"K2V mid-size rounds (stamps build): count {len(mid)}, cycles {sum(c for _, c in mid)}; (S, cycles):", mid)
     sys.exit(0 if match else 3)
 for p in range(2):
     cyc, nb, nl, hp = out[2 + 4 * p: 6 + 4 * p]

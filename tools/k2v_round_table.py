@@ -12,7 +12,12 @@ order-preserving 64-bit key (the 4-byte key), and how often a round's pivot -- t
 is made against -- or the final vec[nth - 1] / vec[nth] shares its bucket with a distinct value (where a 4-byte key
 would decide a comparison differently from the reference's double `<`).
 
-usage: python3 tools/k2v_round_table.py [--scenes N] [--one-wave 1024|2048] [--json out.json]
+`--mid-caps` tabulates the rounds a mid-size phase would take: for every cap M the rounds with
+one_wave < S <= M per pass, the distribution of their Ks, and the share whose Ks exceeds the mailbox that LayA's
+12 288-double array leaves behind an M-position segment (12 288 - M; such a round would exchange in chunks).
+profiles/k2v_midsize_round_table.json is `--scenes 64 --one-wave 2048 --mid-caps 4096,6144,7168,8192,12288`.
+
+usage: python3 tools/k2v_round_table.py [--scenes N] [--one-wave 1024|2048] [--mid-caps M1,M2,...] [--json out.json]
 """
 import argparse
 import json
@@ -107,6 +112,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", type=int, default=16)
     ap.add_argument("--one-wave", type=int, default=1024)
+    ap.add_argument("--mid-caps", default="", help="comma-separated mid-size caps to tabulate (e.g. 4096,6144,7168,8192,12288)")
     ap.add_argument("--json", default="")
     args = ap.parse_args()
     one_wave = args.one_wave
@@ -132,6 +138,27 @@ def main():
             "block_round_ks_over_S_median": round(float(np.median([x[1] / x[0] for x in allb])), 4),
             "block_round_discard_frac_median": round(float(np.median([x[4] / x[0] for x in allb])), 4),
         }
+    if args.mid_caps:
+        kArray = 12288  # LayA's mailbox array: an M-position segment leaves kArray - M doubles of mailbox
+        mid = {}
+        for M in [int(x) for x in args.mid_caps.split(",")]:
+            mid[str(M)] = {"mailbox_left_in_LayA": max(kArray - M, 0)}
+            for P in (0, 1):
+                calls = [r for r in rows if r["pass"] == P]
+                band = [x for r in calls for x in r["rounds"] if one_wave < x[0] <= M]
+                blk = [x for r in calls for x in r["rounds"] if x[0] > one_wave]
+                ks = np.array([x[1] for x in band]) if band else np.zeros(1)
+                mid[str(M)][f"pass{P}"] = {
+                    "rounds_per_call_mean": round(len(band) / len(calls), 2),
+                    "share_of_block_rounds": round(len(band) / max(len(blk), 1), 3),
+                    "calls_with_none": sum(1 for r in calls if not any(one_wave < x[0] <= M for x in r["rounds"])),
+                    "S_sum_per_call_mean": round(sum(x[0] for x in band) / len(calls), 1),
+                    "ks_quantiles_min_p10_p50_p90_max": [int(v) for v in np.percentile(ks, [0, 10, 50, 90, 100])],
+                    "ks_over_S_median": round(float(np.median([x[1] / x[0] for x in band])), 4) if band else 0.0,
+                    "share_ks_above_mailbox_left": round(float(np.mean(ks > max(kArray - M, 0))), 4) if band else 0.0,
+                    "share_ks_above_4352": round(float(np.mean(ks > 4352)), 4) if band else 0.0,
+                }
+        summary["mid_size"] = mid
     tot_pairs = sum(r["pairs_same_key"] for r in rows)
     piv = sum(r["pivots_in_shared_bucket"] for r in rows)
     fin = sum(r["final_in_shared_bucket"] for r in rows)

@@ -405,7 +405,9 @@ int svo_two_view_init(svo_ctx* ctx, const svo_camera* cam, int32_t n_pairs, cons
  * :480-625) for n_problems independent problems.  The reference hands these to g2o, which is not part of its tree;
  * the cost and the schedule below are THIS PROJECT'S CONTRACT, modelled on g2o's OptimizationAlgorithmLevenberg
  * with EdgeProjectXYZ2UV edges, and NOT pinned to g2o's bits.
- *   problem    p owns frames frame_off[p] .. frame_off[p+1]-1 (at most SVO_BA_MAX_FRAMES, each free or fixed),
+ *   problem    p owns frames frame_off[p] .. frame_off[p+1]-1 (each free or fixed; at most SVO_BA_MAX_FRAMES free
+ *              ones, any number of fixed ones: localBA holds every observing frame outside the keyframe list, and a
+ *              point keeps the observers of every frame that ever saw it),
  *              points point_off[p] .. (all free) and observations obs_off[p] .. (frame i, point j, pixel u; i and j
  *              local to the problem).  Observations are grouped by point, points ascending, every point with at
  *              least two and no (frame, point) twice.
@@ -436,7 +438,7 @@ int svo_two_view_init(svo_ctx* ctx, const svo_camera* cam, int32_t n_pairs, cons
  *              order; unused records have iteration -1, trials past the capacity are dropped
  * A problem whose frames are all fixed is a structure-only problem (its reduced system is empty).  Every sum runs
  * in an order fixed by the layout and no floating-point atomics are used: equal inputs give equal bytes.
- * SVO_ERR_ARG: more than SVO_BA_MAX_FRAMES frames in a problem, observations not grouped by ascending point, a
+ * SVO_ERR_ARG: more than SVO_BA_MAX_FRAMES free frames in a problem, observations not grouped by ascending point, a
  * duplicate (frame, point), an index out of range, a point with fewer than two observations.  Synchronous. */
 #define SVO_BA_MAX_FRAMES 16
 #define SVO_BA_TRACE_CAP 64

@@ -205,6 +205,41 @@ def _frozen(v):
     return a
 
 
+# Poses are Sophus::SE3d::params(): qx qy qz qw tx ty tz.  The small per-frame pose algebra of System stays on the host.
+def _quat_rotate(q, v):
+    """q v q^-1 for a unit quaternion (x, y, z, w) and v (3,) or (n, 3), as Eigen's _transformVector forms it."""
+    u = np.cross(q[:3], v)
+    u = u + u
+    return v + q[3] * u + np.cross(q[:3], u)
+
+
+def _quat_mul(a, b):
+    ax, ay, az, aw = a
+    bx, by, bz, bw = b
+    return np.array([aw * bx + ax * bw + ay * bz - az * by, aw * by + ay * bw + az * bx - ax * bz,
+                     aw * bz + az * bw + ax * by - ay * bx, aw * bw - ax * bx - ay * by - az * bz])
+
+
+def _norm3(d):
+    """|d| with the sum in a fixed order (the C++ mirror forms the same bits)."""
+    return math.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])
+
+
+def pose_inverse(p):
+    """Sophus::SE3d::inverse() on params."""
+    p = np.asarray(p, np.float64)
+    qi = p[:4] * np.array([-1.0, -1.0, -1.0, 1.0])
+    return np.concatenate([qi, -_quat_rotate(qi, p[4:])])
+
+
+def pose_compose(a, b):
+    """Sophus::SE3d a * b on params (the product quaternion renormalised)."""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    q = _quat_mul(a[:4], b[:4])
+    q = q / math.sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3])
+    return np.concatenate([q, a[4:] + _quat_rotate(a[:4], b[4:])])
+
+
 class PointType:  # Point::PointType (include/point.hpp:18-24)
     GOOD, DELETED, CANDIDATE, UNKNOWN = 0, 1, 2, 3
 
@@ -455,8 +490,32 @@ class Frame:
         self.features = []
         self.last_keyframe = last_keyframe
         self.timestamp = timestamp
+        self.key_frame = False  # m_keyFrame
         self.id = Frame._frame_counter
         Frame._frame_counter += 1
+
+    def set_keyframe(self):  # src/frame.cpp:29-32
+        self.key_frame = True
+
+    def is_keyframe(self):  # src/frame.cpp:78-81
+        return self.key_frame
+
+    def number_observation_with_points(self):  # src/frame.cpp:56-67
+        return int(np.count_nonzero(_point_rows(self.features) >= 0))
+
+    def world2camera(self, point):  # src/frame.cpp:89-92
+        q, t = self.abs_pose[:4], self.abs_pose[4:]
+        return _quat_rotate(q, np.asarray(point, np.float64)) + t
+
+    def camera_in_world(self):  # src/frame.cpp:116-120: C = -R^T t
+        q = self.abs_pose[:4] * np.array([-1.0, -1.0, -1.0, 1.0])
+        return -_quat_rotate(q, self.abs_pose[4:])
+
+    def is_visible(self, point):  # src/frame.cpp:69-76
+        pc = self.world2camera(point)
+        if pc[2] < 0.0:
+            return False
+        return bool(self.camera.is_in_frame(self.camera.project2d(pc)))
 
     def world2image(self, points):
         """Frame::world2image (src/frame.cpp:83-92) for an (n, 3) array (or one point)."""
@@ -814,6 +873,69 @@ class Map:
     def cell_of(self, px):
         return int(px[1]) // self.cell_size * self.grid_cols + int(px[0]) // self.cell_size
 
+    def reset(self):  # src/map.cpp:21-24
+        self.key_frames.clear()
+
+    def add_keyframe(self, frame):  # src/map.cpp:112-115
+        self.key_frames.append(frame)
+
+    def size_keyframes(self):  # src/map.cpp:218-221
+        return len(self.key_frames)
+
+    def get_close_keyframes(self, frame):
+        """getCloseKeyframes (src/map.cpp:144-170): the keyframes in reverse order, `frame` itself skipped; a
+        keyframe is listed with |frame.t - keyframe.t| (absPose.translation(), not the camera centres) as soon as
+        one of its features' points is visible in `frame`.  The reference dereferences m_point unchecked there; a
+        feature without a point is passed over here."""
+        out = []
+        for kf in reversed(self.key_frames):
+            if kf is frame:
+                continue
+            for f in kf.features:
+                if f.point is not None and frame.is_visible(f.point.position):
+                    out.append((kf, _norm3(frame.abs_pose[4:] - kf.abs_pose[4:])))
+                    break
+        return out
+
+    def get_closest_keyframe(self, frame):
+        """getClosestKeyframe (src/map.cpp:117-142): the first close keyframe with the strictly smallest distance,
+        or None."""
+        closest, min_distance = None, float("inf")
+        for kf, d in self.get_close_keyframes(frame):
+            if kf is not frame and d < min_distance:
+                min_distance, closest = d, kf
+        return closest
+
+    def get_furthest_keyframe(self, pos):
+        """getFurthestKeyframe (src/map.cpp:172-184): the first keyframe whose camera centre is strictly furthest
+        from pos (None when every distance is 0)."""
+        pos = np.asarray(pos, np.float64)
+        furthest, max_distance = None, 0.0
+        for kf in self.key_frames:
+            dist = _norm3(kf.camera_in_world() - pos)
+            if dist > max_distance:
+                max_distance, furthest = dist, kf
+        return furthest
+
+    def remove_frame(self, frame):
+        """removeFrame (src/map.cpp:26-61): every feature of the keyframe leaves its point's observer list
+        (Point::removeFrame) and loses the point, the frame's features and last keyframe are dropped, the frame
+        leaves the keyframe list, and the candidates seeded from it leave too (removeFrameCandidate, :669-675).  A
+        point is not deleted here, whatever number of observers it keeps."""
+        for i, fr in enumerate(self.key_frames):
+            if fr is frame:
+                for f in fr.features:
+                    if f.point is not None:
+                        f.point.remove_frame(f.frame)
+                        f.point = None
+                break
+        else:
+            raise ValueError("remove_frame: not a keyframe of this map")  # (the reference erases past the end)
+        frame.features.clear()
+        frame.last_keyframe = None
+        del self.key_frames[i]
+        self.candidates = [c for c in self.candidates if c[0].frame is not frame]
+
     def remove_point(self, point):  # src/map.cpp:76-87
         for feature in point.features:
             feature.frame.remove_feature(feature)
@@ -986,14 +1108,50 @@ class DepthEstimator:
     update_filters = updateFilters (:192-309).  Converged seeds become candidates (Map::addNewCandidate,
     src/map.cpp:586-593): (feature, Point) pairs in the reference's order."""
 
-    def __init__(self, ctx=None):
+    def __init__(self, ctx=None, map=None):
         self.ctx = ctx or default_context()
+        self.map = map        # m_map: add_frame hands the converged seeds to it (None: they stay in candidates)
         self.keyframes = []   # Frame objects; seed["kf"] indexes this list
         self.features = []    # the Feature behind every seed, same order as self.seeds
         self.seeds = np.zeros(0, DEPTH_SEED)
         self.candidates = []
+        self._deleted_keyframe = None  # m_deletedKeyframe
+
+    def reset(self):  # src/depth_estimator.cpp:99-109
+        self.keyframes, self.features, self.seeds = [], [], np.zeros(0, DEPTH_SEED)
+        self._deleted_keyframe = None
+
+    def remove_keyframe(self, frame):
+        """removeKeyframe (src/depth_estimator.cpp:88-92): the frame is buffered; its seeds leave at the next
+        add_frame / add_keyframe (the reference's worker drops them before its next update, :145-148, :161-173)."""
+        self._deleted_keyframe = frame
+
+    def _drop_deleted_keyframe(self):
+        frame, self._deleted_keyframe = self._deleted_keyframe, None
+        if frame is None:
+            return
+        keep = [i for i, f in enumerate(self.features) if f.frame is not frame]
+        self.features = [self.features[i] for i in keep]
+        self.seeds = self.seeds[keep].copy() if keep else np.zeros(0, DEPTH_SEED)
+        remap = np.full(len(self.keyframes), -1, np.int32)  # the keyframe table without the frame
+        kept = [k for k, kf in enumerate(self.keyframes) if kf is not frame]
+        remap[kept] = np.arange(len(kept), dtype=np.int32)
+        self.keyframes = [self.keyframes[k] for k in kept]
+        if len(self.seeds):
+            self.seeds["kf"] = remap[self.seeds["kf"]]
+
+    def add_frame(self, frame):
+        """addFrame (src/depth_estimator.cpp:50-65), the m_thread == nullptr branch: updateFilters(frame), the
+        converged seeds handed to the map (Map::addNewCandidate, :288).  Returns them."""
+        self._drop_deleted_keyframe()
+        new = self.update_filters(frame)
+        if self.map is not None:
+            for feature, point in new:
+                self.map.add_new_candidate(feature, point)
+        return new
 
     def add_keyframe(self, frame, depth_mean, depth_min):
+        self._drop_deleted_keyframe()
         feats = [f for f in frame.features if f.point is None]
         kf = len(self.keyframes)
         self.keyframes.append(frame)
@@ -1152,7 +1310,7 @@ class BundleAdjustResult:
     __slots__ = ("obs_chi2", "init_chi", "final_chi", "iterations", "status", "trace")
 
 
-BA_MAX_FRAMES = 16  # SVO_BA_MAX_FRAMES
+BA_MAX_FRAMES = 16  # SVO_BA_MAX_FRAMES: free frames per problem (fixed frames are not limited)
 BA_TRACE_CAP = 64   # SVO_BA_TRACE_CAP
 
 
@@ -1230,8 +1388,9 @@ class BundleAdjustment:
         (frame index, point index, feature; grouped by point), 10 iterations with Huber width reprojection_error;
         poses of the free frames and all positions written back, then Map.remove_feature for every edge whose
         e2 exceeds reprojection_error^2, in edge order.  Returns (init chi, final chi, edges over the threshold)."""
-        if len(frames) > BA_MAX_FRAMES:
-            raise ValueError(f"bundle adjustment over {len(frames)} frames (at most {BA_MAX_FRAMES})")
+        n_free = len(frames) - int(np.count_nonzero(fixed))
+        if n_free > BA_MAX_FRAMES:  # (fixed frames are not limited)
+            raise ValueError(f"bundle adjustment over {n_free} frames free to move (at most {BA_MAX_FRAMES})")
         poses = np.array([np.asarray(f.abs_pose, np.float64).reshape(7) for f in frames], np.float64).reshape(-1, 7)
         rows = np.fromiter((p._i for p in points), np.int64, count=len(points))
         pos = np.ascontiguousarray(_PT.pos[rows], np.float64).reshape(-1, 3)
@@ -1279,7 +1438,7 @@ class BundleAdjustment:
         becomes a fixed frame; StructureOnlySolver first (10 iterations), then 10 joint iterations; write back;
         map.remove_feature for every edge over the threshold.  The reference walks a std::set of shared_ptr, that
         is, the points in pointer order; here they are taken in first-seen order (keyframe order, then feature
-        order), so the result does not depend on the allocator.  More than 16 frames in the problem raises."""
+        order), so the result does not depend on the allocator.  More than 16 keyframes raise."""
         frames = list(map.key_frames)
         index = {id(fr): i for i, fr in enumerate(frames)}
         n_key = len(frames)
@@ -1525,3 +1684,361 @@ def compute_essential_matrix(ref_frame, cur_frame, repro_error, threshold_corres
     ok = (ref_frame.number_observation() > threshold_corresponding_points and
           cur_frame.number_observation() > threshold_corresponding_points)
     return ok, r.E[0].copy()
+
+
+# ---------------------------------------------------------------- the tracker: algorithm:: scalars and System
+def compute_relative_pose(ref_frame, cur_frame):
+    """algorithm::computeRelativePose (src/algorithm.cpp:705-709): T_cur_ref = cur.absPose * ref.absPose^-1."""
+    return pose_compose(cur_frame.abs_pose, pose_inverse(ref_frame.abs_pose))
+
+
+def normalized_depth_camera(frame):
+    """algorithm::normalizedDepthCamera(frame, out) (src/algorithm.cpp:601-608): |world2camera(point)| of every
+    feature (each must have a point)."""
+    if not len(frame.features):
+        return np.zeros(0)
+    rows = _point_rows(frame.features)
+    if (rows < 0).any():
+        raise ValueError("normalized_depth_camera: a feature without a point (the reference dereferences it)")
+    pc = _quat_rotate(frame.abs_pose[:4], _PT.pos[rows]) + frame.abs_pose[4:]
+    return np.sqrt((pc[:, 0] * pc[:, 0] + pc[:, 1] * pc[:, 1]) + pc[:, 2] * pc[:, 2])
+
+
+def _nth_element(a, nth):
+    """libstdc++'s std::nth_element(a, a + nth, a + len(a)) on a list of floats, in place: introselect (median of
+    three to the front, unguarded Hoare partition, heap select after 2 log2 n rounds, insertion sort of the last
+    <= 3), so that a[nth - 1] is what the reference reads for an even length (tests/test_system.py checks it against
+    the toolchain's own function)."""
+    first, last = 0, len(a)
+    if first == last or nth == last:
+        return
+    depth = 2 * (last.bit_length() - 1)
+    while last - first > 3:
+        if depth == 0:  # __heap_select(first, nth + 1, last); iter_swap(first, nth)
+            middle = nth + 1
+
+            def adjust(hole, n, value):  # __adjust_heap + __push_heap on a[first:first + n]
+                top, child = hole, hole
+                while child < (n - 1) // 2:
+                    child = 2 * (child + 1)
+                    if a[first + child] < a[first + child - 1]:
+                        child -= 1
+                    a[first + hole] = a[first + child]
+                    hole = child
+                if n % 2 == 0 and child == (n - 2) // 2:
+                    child = 2 * (child + 1)
+                    a[first + hole] = a[first + child - 1]
+                    hole = child - 1
+                parent = (hole - 1) // 2
+                while hole > top and a[first + parent] < value:
+                    a[first + hole] = a[first + parent]
+                    hole = parent
+                    parent = (hole - 1) // 2
+                a[first + hole] = value
+
+            n = middle - first
+            if n >= 2:  # __make_heap
+                parent = (n - 2) // 2
+                while True:
+                    adjust(parent, n, a[first + parent])
+                    if parent == 0:
+                        break
+                    parent -= 1
+            for i in range(middle, last):
+                if a[i] < a[first]:  # __pop_heap(first, middle, i)
+                    value = a[i]
+                    a[i] = a[first]
+                    adjust(0, n, value)
+            a[first], a[nth] = a[nth], a[first]
+            return
+        depth -= 1
+        mid = first + (last - first) // 2
+        x, y, z = first + 1, mid, last - 1  # __move_median_to_first(first, first + 1, mid, last - 1)
+        if a[x] < a[y]:
+            m = y if a[y] < a[z] else (z if a[x] < a[z] else x)
+        else:
+            m = x if a[x] < a[z] else (z if a[y] < a[z] else y)
+        a[first], a[m] = a[m], a[first]
+        pivot = a[first]
+        lo, hi = first + 1, last  # __unguarded_partition(first + 1, last, first)
+        while True:
+            while a[lo] < pivot:
+                lo += 1
+            hi -= 1
+            while pivot < a[hi]:
+                hi -= 1
+            if not lo < hi:
+                break
+            a[lo], a[hi] = a[hi], a[lo]
+            lo += 1
+        if lo <= nth:
+            first = lo
+        else:
+            last = lo
+    for i in range(first + 1, last):  # __insertion_sort
+        v = a[i]
+        j = i
+        while j > first and v < a[j - 1]:
+            a[j] = a[j - 1]
+            j -= 1
+        a[j] = v
+
+
+def compute_median(values):
+    """algorithm::computeMedian(input) (src/algorithm.cpp:813-832): std::nth_element at size / 2; an even length
+    averages vec[mid - 1], as nth_element left it, with vec[mid]; NaN for an empty input."""
+    vec = np.asarray(values, np.float64).reshape(-1).tolist()
+    if not vec:
+        return float("nan")
+    mid = len(vec) // 2
+    _nth_element(vec, mid)
+    return vec[mid] if len(vec) % 2 else (vec[mid - 1] + vec[mid]) / 2.0
+
+
+def compute_number_projected_points(cur_frame):
+    """algorithm::computeNumberProjectedPoints (src/algorithm.cpp:783-804): the features with a point whose bearing,
+    stretched to the point's distance from the camera centre and moved by T_cur_lastKeyframe, projects inside the
+    5-px border."""
+    rel = compute_relative_pose(cur_frame.last_keyframe, cur_frame)
+    C = cur_frame.camera_in_world()
+    cam = cur_frame.camera
+    n = 0
+    for f in cur_frame.features:
+        if f.point is None:
+            continue
+        cur_point = _quat_rotate(rel[:4], f.bearing_vec * _norm3(f.point.position - C)) + rel[4:]
+        if cam.is_in_frame(cam.project2d(cur_point), 5.0):
+            n += 1
+    return n
+
+
+class Config:
+    """The fields of the reference's Config (include/config.hpp) that src/system.cpp reads, with the defaults of its
+    config/config.json and resource/kitti.yaml, plus what this project adds: ransac_seed (the RANSAC sampler),
+    map_cell_seed (the map's cell order), max_keyframes (the literal 7 of src/system.cpp:436) and median_mode
+    (ImageAlignment's robust scale).  Visualisation and logging are not part of it."""
+
+    def __init__(self, **kw):
+        self.img_width, self.img_height = 1241, 376
+        self.fx = self.fy = 721.5377
+        self.cx, self.cy = 609.5593, 172.8540
+        self.patch_size_optical_flow = 11
+        self.patch_size_image_alignment = 5
+        self.min_level_image_pyramid = 0
+        self.max_level_image_pyramid = 3
+        self.cell_pixel_size = 30
+        self.threshold_gradient_magnitude = 50
+        self.desired_detected_points_for_initialization = 200
+        self.min_detected_points_success_initialization = 100
+        self.disparity_threshold = 5.0
+        self.init_map_scale_factor = 1.0
+        self.ransac_seed = 0
+        self.map_cell_seed = 0
+        self.max_keyframes = 7
+        self.median_mode = MEDIAN_REFERENCE
+        for k, v in kw.items():
+            if not hasattr(self, k):
+                raise TypeError(f"Config has no field {k!r}")
+            setattr(self, k, v)
+
+
+class System:
+    """System(config) (include/system.hpp, src/system.cpp:15-511): the state machine that turns images into poses,
+    addImage -> processFirstFrame / processSecondFrame / processNewFrame / relocalisation, each step one of the
+    device-backed classes above in the reference's order.
+
+    Deliberate differences from the reference:
+      * the depth estimator runs without its worker thread, i.e. the reference's own m_thread == nullptr branch
+        (addFrame = updateFilters, addKeyframe = initializeFilters), so a run is a function of its images and seeds;
+      * the seed-age rule (src/depth_estimator.cpp:220) compares a static counter the reference never advances: it
+        is inert there and absent here;
+      * the map's cell order and the RANSAC samples are seeded (Config.map_cell_seed, Config.ransac_seed) where
+        the reference draws from std::random_device / cv::RNG;
+      * DepthEstimator.remove_keyframe takes effect at the next add_frame / add_keyframe (there: at the worker's
+        next update).
+    Visualisation and logging are left out; report_summary returns the counts."""
+
+    # System::Status / System::Result (include/system.hpp:23-38; "Procese" is the reference's spelling)
+    PROCESS_FIRST_FRAME, PROCESS_SECOND_FRAME, PROCESS_NEW_FRAME, PROCESS_RELOCALIZATION = 0, 1, 2, 3
+    SUCCESS, FAILED, KEYFRAME = 0, 1, 2
+
+    def __init__(self, config=None, ctx=None, instrument=False):  # :15-32
+        c = self.config = config or Config()
+        self.instrument = bool(instrument)  # fill timings and ba_removed (tests, tools/system_time.py); off: no cost
+        self.ctx = ctx or default_context()
+        self.camera = PinholeCamera(c.img_width, c.img_height, c.fx, c.fy, c.cx, c.cy)
+        self.alignment = ImageAlignment(c.patch_size_image_alignment, c.min_level_image_pyramid,
+                                        c.max_level_image_pyramid, 6, self.ctx, c.median_mode)
+        self.feature_selector = FeatureSelection(c.img_width, c.img_height, c.cell_pixel_size, self.ctx)
+        self.map = Map(self.camera, c.cell_pixel_size, c.map_cell_seed, self.ctx)
+        self.depth_estimator = DepthEstimator(self.ctx, self.map)
+        self.bundler = BundleAdjustment(self.camera, 0, 6, self.ctx)
+        self.active_keyframe = None
+        self.ref_frame = None
+        self.cur_frame = None
+        self.prediction_relative_pose = np.array([0, 0, 0, 1, 0, 0, 0], np.float64)
+        self.status = System.PROCESS_FIRST_FRAME
+        self.last_result = System.FAILED
+        self.ba_removed = []   # instrument: (frame id, feature index before the BA) of what the last BA removed
+        self.timings = {}      # instrument: host seconds per step of the last add_image
+
+    def set_status(self, status):
+        """The relocalisation branch is never entered by the reference itself (nothing sets the status): tests and
+        callers reach it through this setter."""
+        self.status = int(status)
+
+    def _timed(self, name, fn, *a):
+        if not self.instrument:
+            return fn(*a)
+        t0 = time.perf_counter()
+        r = fn(*a)
+        self.timings[name] = self.timings.get(name, 0.0) + time.perf_counter() - t0
+        return r
+
+    def add_image(self, img, timestamp=0):  # :34-76
+        if self.instrument:
+            self.timings, self.ba_removed = {}, []
+        c = self.config
+        self.cur_frame = self._timed("frame", Frame, self.camera, img, c.max_level_image_pyramid + 1, timestamp,
+                                     self.active_keyframe, self.ctx)
+        res = System.FAILED
+        if self.status == System.PROCESS_NEW_FRAME:
+            res = self.process_new_frame()
+        elif self.status == System.PROCESS_SECOND_FRAME:
+            res = self.process_second_frame()
+        elif self.status == System.PROCESS_FIRST_FRAME:
+            res = self.process_first_frame()
+        elif self.status == System.PROCESS_RELOCALIZATION:
+            res = self.relocalize_frame(self.map.get_closest_keyframe(self.cur_frame))
+        if self.ref_frame is not None:
+            self.prediction_relative_pose = compute_relative_pose(self.ref_frame, self.cur_frame)
+        self.last_result = res
+        if res == System.FAILED:
+            return False
+        self.ref_frame = self.cur_frame
+        return True
+
+    def _select(self, frame):
+        c = self.config
+        self._timed("select", self.feature_selector.gradient_magnitude_with_ssc, frame, c.threshold_gradient_magnitude,
+                    c.desired_detected_points_for_initialization, True)
+
+    def process_first_frame(self):  # :78-115
+        c, cur = self.config, self.cur_frame
+        self._select(cur)
+        if cur.number_observation() < c.min_detected_points_success_initialization:
+            return System.FAILED
+        cur.set_keyframe()
+        self.active_keyframe = cur
+        self.map.add_keyframe(cur)
+        self.status = System.PROCESS_SECOND_FRAME
+        return System.SUCCESS
+
+    def _run_ba(self, frames, fn, *a):
+        """fn(*a) (a windowed BA) with ba_removed <- the features it removed from `frames`."""
+        if not self.instrument:
+            return fn(*a)
+        before = [(fr, list(fr.features)) for fr in frames]
+        r = self._timed("ba", fn, *a)
+        for fr, feats in before:
+            left = {id(f) for f in fr.features}
+            self.ba_removed += [(fr.id, i) for i, f in enumerate(feats) if id(f) not in left]
+        return r
+
+    def process_second_frame(self):  # :117-302
+        c, ref, cur = self.config, self.ref_frame, self.cur_frame
+        if not self._timed("klt", compute_optical_flow_sparse, ref, cur, c.patch_size_optical_flow,
+                           c.disparity_threshold, self.ctx):
+            return System.FAILED
+        threshold = int(c.min_detected_points_success_initialization * 0.5)
+        ok, E = self._timed("essential", compute_essential_matrix, ref, cur, 1.0, threshold, c.ransac_seed, self.ctx)
+        if not ok:
+            return System.FAILED
+        ok, _, _ = self._timed("two_view", two_view_initialize, ref, cur, E, c.init_map_scale_factor,
+                               c.cell_pixel_size, self.ctx)
+        if not ok:
+            return System.FAILED
+        self._run_ba([ref, cur], self.bundler.two_view_ba, ref, cur, self.map, 2.0)
+        cur.set_keyframe()
+        self.active_keyframe = cur
+        depths = normalized_depth_camera(cur)
+        median_depth = compute_median(depths)
+        min_depth = float(depths.min())
+        self.feature_selector.set_existing_features(cur.features)
+        self._select(cur)
+        self.depth_estimator.add_keyframe(cur, median_depth, 0.5 * min_depth)
+        self.map.add_keyframe(cur)
+        self.status = System.PROCESS_NEW_FRAME
+        return System.SUCCESS
+
+    def process_new_frame(self):  # :304-446
+        ref, cur = self.ref_frame, self.cur_frame
+        cur.abs_pose = pose_compose(self.prediction_relative_pose, ref.abs_pose)
+        self._timed("align", self.alignment.align, ref, cur)
+        self._timed("reproject", self.map.reproject_map, ref, cur, [])
+        self._timed("candidates", self.map.add_candidate_to_frame, cur)
+        if not self.compute_tracking_quality(cur, ref.number_observation_with_points()):
+            cur.abs_pose = np.array(ref.abs_pose, np.float64)
+            return System.SUCCESS
+        depths = normalized_depth_camera(cur)
+        depth_mean = compute_median(depths)
+        depth_min = float(depths.min())
+        if self.need_keyframe(depths, depth_mean):
+            self._timed("depth", self.depth_estimator.add_frame, cur)
+            return System.SUCCESS
+        cur.set_keyframe()
+        self.map.add_keyframe(cur)
+        self.active_keyframe = cur
+        self._run_ba(list(self.map.key_frames), self.bundler.local_ba, self.map, 2.0)
+        self.feature_selector.set_existing_features(cur.features)
+        self._select(cur)
+        self.depth_estimator.add_keyframe(cur, depth_mean, depth_min * 0.5)
+        if self.map.size_keyframes() > self.config.max_keyframes:  # :436-442
+            furthest = self.map.get_furthest_keyframe(cur.camera_in_world())
+            self.depth_estimator.remove_keyframe(furthest)
+            self.map.remove_frame(furthest)
+        return System.KEYFRAME
+
+    def relocalize_frame(self, closest_keyframe):
+        """relocalizeFrame (:448-457).  A closest keyframe without a last keyframe (the very first one) raises in
+        ImageAlignment.align, where the reference dereferences the null pointer."""
+        if closest_keyframe is None:
+            return System.FAILED
+        self._timed("align", self.alignment.align, closest_keyframe, self.cur_frame)
+        return System.SUCCESS
+
+    @staticmethod
+    def compute_tracking_quality(frame, ref_frame_number_observations):  # :459-472
+        cur = frame.number_observation()
+        if cur < 50:
+            return False
+        return not (int(ref_frame_number_observations) - cur > 40)
+
+    def need_keyframe(self, depths_in_cur_frame, scene_depth_mean):
+        """needKeyframe (:474-511).  As in the reference, True means that NO keyframe is needed: diffId < 3 (the
+        other quantities it computes only feed its log)."""
+        cur = self.cur_frame
+        return cur.id - cur.last_keyframe.id < 3
+
+    def write_in_file(self, f):  # :635-640
+        from . import trajectory
+        trajectory.write_in_file(self.ref_frame, f)
+
+    def report_summary(self):
+        """reportSummary (:513-552) as a dict instead of log lines.  The reference walks m_allFrames, which it never
+        fills; here the frames are the keyframes of the map and the reference / current frame."""
+        frames = list(self.map.key_frames)
+        for fr in (self.ref_frame, self.cur_frame):
+            if fr is not None and all(fr is not k for k in frames):
+                frames.append(fr)
+        points, n_features = set(), 0
+        rows = []
+        for fr in frames:
+            n_features += fr.number_observation()
+            points.update(id(f.point) for f in fr.features if f.point is not None)
+            rows.append(dict(id=fr.id, keyframe=fr.is_keyframe(), features=fr.number_observation(),
+                             features_with_points=fr.number_observation_with_points(),
+                             last_keyframe=-1 if fr.last_keyframe is None else fr.last_keyframe.id))
+        return dict(frames=rows, features=n_features, points=len(points),
+                    filters=self.depth_estimator.number_filters(), candidates=len(self.map.candidates),
+                    keyframes=self.map.size_keyframes())

@@ -28,7 +28,7 @@ namespace svo {
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kMaxF = SVO_BA_MAX_FRAMES;
+constexpr int kMaxF = SVO_BA_MAX_FRAMES;  // free frames of a problem; fixed frames are not limited
 constexpr int kMaxN = 6 * kMaxF;
 constexpr int kFailLimit = 5;  // trials after a failure (setMaxTrialsAfterFailure(5), :330)
 
@@ -133,22 +133,30 @@ struct JointShared {
     double U[kMaxF][21];
     double b[kMaxN];
     double x[kMaxN];                    // rhs, then dp
-    double pose[2][kMaxF][7];           // [0] the estimate, [1] the trial
+    double pose[2][kMaxF][7];           // of the free frames, by reduced index: [0] the estimate, [1] the trial
     BAPose T[2][kMaxF];
     double red[2][kThreads];
-    int32_t ridx[kMaxF];                // reduced index of a frame, -1 when fixed
     int32_t fre[kMaxF];                 // frame of a reduced index
     int32_t flag;
 };
 
+// the transform of frame i: a free frame's from LDS (estimate or trial), a fixed frame's from its pose as given (it
+// never changes; the same ba_pose on the same seven doubles, so the same bits wherever it is formed)
+__device__ __forceinline__ BAPose frame_T(const JointShared& sh, const int32_t* ridx, const double* gposes, int which,
+                                          int i) {
+    const int32_t r = ridx[i];
+    return r >= 0 ? sh.T[which][r] : ba_pose(gposes + 7 * (int64_t)i);
+}
+
 // the robust chi of the problem at T[which] / X; also sums `extra` (returned in it)
-__device__ double robust_chi(const BundleAdjustArgs& a, JointShared& sh, int which, const double* X, int32_t P,
-                             const int32_t* pobs, int32_t obase, const int32_t* of, const double* px, double& extra) {
+__device__ double robust_chi(const BundleAdjustArgs& a, JointShared& sh, const int32_t* ridx, const double* gposes,
+                             int which, const double* X, int32_t P, const int32_t* pobs, int32_t obase,
+                             const int32_t* of, const double* px, double& extra) {
     double part = 0.0;
     for (int j = threadIdx.x; j < P; j += kThreads) {
         const V3 Xj = ld3(X + 3 * (int64_t)j);
         for (int32_t o = pobs[j] - obase; o < pobs[j + 1] - obase; ++o) {
-            const BAEdge e = ba_edge(ba_transform(sh.T[which][of[o]], Xj), a.f, a.cx, a.cy, px[2 * (int64_t)o],
+            const BAEdge e = ba_edge(ba_transform(frame_T(sh, ridx, gposes, which, of[o]), Xj), a.f, a.cx, a.cy, px[2 * (int64_t)o],
                                      px[2 * (int64_t)o + 1], a.delta);
             part += e.rho;
         }
@@ -177,7 +185,7 @@ __global__ void __launch_bounds__(kThreads) ba_joint_kernel(BundleAdjustArgs a) 
         return;
     }
     double* gposes = a.poses + 7 * (int64_t)a.frame_off[p];
-    const uint8_t* fixed = a.frame_fixed + a.frame_off[p];
+    const int32_t* ridx = a.ridx + a.frame_off[p];  // reduced index of a frame, -1 when fixed (built by the host)
     const int64_t pbase = a.point_off[p];
     double* X = a.points + 3 * pbase;
     double* Xt = a.Xt + 3 * pbase;
@@ -194,26 +202,24 @@ __global__ void __launch_bounds__(kThreads) ba_joint_kernel(BundleAdjustArgs a) 
     // ---- layout: reduced indices, the frames x points table, the poses
     if (tid == 0) {
         int n = 0;
-        for (int i = 0; i < F; ++i) {
-            sh.ridx[i] = fixed[i] ? -1 : n;
-            if (!fixed[i]) sh.fre[n++] = i;
-        }
+        for (int i = 0; i < F; ++i)
+            if (ridx[i] >= 0) sh.fre[n++] = i;  // (ridx counts the free frames in order: ridx[i] == n here)
         sh.flag = n;
     }
     for (int64_t i = tid; i < (int64_t)F * P; i += kThreads) tab[i] = -1;
-    if (tid < F) {
-        for (int k = 0; k < 7; ++k) sh.pose[0][tid][k] = gposes[7 * tid + k];
-        sh.T[0][tid] = ba_pose(sh.pose[0][tid]);
-    }
     __syncthreads();
     const int nfree = sh.flag;
     const int n = 6 * nfree;
+    if (tid < nfree) {
+        for (int k = 0; k < 7; ++k) sh.pose[0][tid][k] = gposes[7 * sh.fre[tid] + k];
+        sh.T[0][tid] = ba_pose(sh.pose[0][tid]);
+    }
     for (int j = tid; j < P; j += kThreads)
         for (int32_t o = pobs[j] - obase; o < pobs[j + 1] - obase; ++o) tab[(int64_t)j * F + of[o]] = o;
     __syncthreads();
 
     double zero = 0.0;
-    double cur = robust_chi(a, sh, 0, X, P, pobs, obase, of, px, zero);
+    double cur = robust_chi(a, sh, ridx, gposes, 0, X, P, pobs, obase, of, px, zero);
     if (tid == 0) a.init_chi[p] = cur;
     double lambda = 0.0, nu = 2.0;
     int32_t iters = 0, status = 0, ntrace = 0;
@@ -227,10 +233,11 @@ __global__ void __launch_bounds__(kThreads) ba_joint_kernel(BundleAdjustArgs a) 
             V3 g{0.0, 0.0, 0.0};
             for (int32_t o = pobs[j] - obase; o < pobs[j + 1] - obase; ++o) {
                 const int i = of[o];
-                const V3 c = ba_transform(sh.T[0][i], Xj);
+                const BAPose Ti = frame_T(sh, ridx, gposes, 0, i);
+                const V3 c = ba_transform(Ti, Xj);
                 const BAEdge e = ba_edge(c, a.f, a.cx, a.cy, px[2 * (int64_t)o], px[2 * (int64_t)o + 1], a.delta);
                 double Jp[2][6], Jx[2][3];
-                ba_jacobians(sh.T[0][i], c, a.f, Jp, Jx);
+                ba_jacobians(Ti, c, a.f, Jp, Jx);
                 V[0] += e.w * (Jx[0][0] * Jx[0][0] + Jx[1][0] * Jx[1][0]);
                 V[1] += e.w * (Jx[0][0] * Jx[0][1] + Jx[1][0] * Jx[1][1]);
                 V[2] += e.w * (Jx[0][0] * Jx[0][2] + Jx[1][0] * Jx[1][2]);
@@ -240,7 +247,7 @@ __global__ void __launch_bounds__(kThreads) ba_joint_kernel(BundleAdjustArgs a) 
                 g.x += e.w * (Jx[0][0] * e.ex + Jx[1][0] * e.ey);
                 g.y += e.w * (Jx[0][1] * e.ex + Jx[1][1] * e.ey);
                 g.z += e.w * (Jx[0][2] * e.ex + Jx[1][2] * e.ey);
-                if (sh.ridx[i] >= 0) {
+                if (ridx[i] >= 0) {
                     double* ed = edge + 15 * (int64_t)o;
                     double* w = W + 18 * (int64_t)o;
                     for (int k = 0; k < 6; ++k) {
@@ -379,13 +386,9 @@ __global__ void __launch_bounds__(kThreads) ba_joint_kernel(BundleAdjustArgs a) 
                 }
                 __syncthreads();
                 // the trial's poses
-                if (tid < F) {
-                    if (sh.ridx[tid] >= 0) {
-                        const SE3 Tn = se3_compose(se3_exp(&sh.x[6 * sh.ridx[tid]]), se3_load(sh.pose[0][tid]));
-                        se3_store(Tn, sh.pose[1][tid]);
-                    } else {
-                        for (int k = 0; k < 7; ++k) sh.pose[1][tid][k] = sh.pose[0][tid][k];
-                    }
+                if (tid < nfree) {
+                    const SE3 Tn = se3_compose(se3_exp(&sh.x[6 * tid]), se3_load(sh.pose[0][tid]));
+                    se3_store(Tn, sh.pose[1][tid]);
                     sh.T[1][tid] = ba_pose(sh.pose[1][tid]);
                 }
                 // the trial's points: dx_j = (V_j + lambda I)^-1 (g_j - sum_i W_ij^T dp_i)
@@ -394,7 +397,7 @@ __global__ void __launch_bounds__(kThreads) ba_joint_kernel(BundleAdjustArgs a) 
                     const double* vg = Vg + 9 * (int64_t)j;
                     V3 h{vg[6], vg[7], vg[8]};
                     for (int32_t o = pobs[j] - obase; o < pobs[j + 1] - obase; ++o) {
-                        const int ri = sh.ridx[of[o]];
+                        const int ri = ridx[of[o]];
                         if (ri < 0) continue;
                         const double* w = W + 18 * (int64_t)o;
                         for (int k = 0; k < 6; ++k) {
@@ -412,7 +415,7 @@ __global__ void __launch_bounds__(kThreads) ba_joint_kernel(BundleAdjustArgs a) 
                     sc += d.x * (lambda * d.x + vg[6]) + d.y * (lambda * d.y + vg[7]) + d.z * (lambda * d.z + vg[8]);
                 }
                 __syncthreads();
-                tmp = robust_chi(a, sh, 1, Xt, P, pobs, obase, of, px, sc);
+                tmp = robust_chi(a, sh, ridx, gposes, 1, Xt, P, pobs, obase, of, px, sc);
                 double scale = 0.0;
                 for (int k = 0; k < n; ++k) scale += sh.x[k] * (lambda * sh.x[k] + sh.b[k]);
                 scale = (scale + sc) + 1e-3;
@@ -428,7 +431,7 @@ __global__ void __launch_bounds__(kThreads) ba_joint_kernel(BundleAdjustArgs a) 
                 __syncthreads();
                 for (int j = tid; j < P; j += kThreads)
                     for (int k = 0; k < 3; ++k) X[3 * (int64_t)j + k] = Xt[3 * (int64_t)j + k];
-                if (tid < F) {
+                if (tid < nfree) {
                     for (int k = 0; k < 7; ++k) sh.pose[0][tid][k] = sh.pose[1][tid][k];
                     sh.T[0][tid] = sh.T[1][tid];
                 }
@@ -450,13 +453,13 @@ __global__ void __launch_bounds__(kThreads) ba_joint_kernel(BundleAdjustArgs a) 
     for (int j = tid; j < P; j += kThreads) {
         const V3 Xj = ld3(X + 3 * (int64_t)j);
         for (int32_t o = pobs[j] - obase; o < pobs[j + 1] - obase; ++o) {
-            const BAEdge e = ba_edge(ba_transform(sh.T[0][of[o]], Xj), a.f, a.cx, a.cy, px[2 * (int64_t)o],
-                                     px[2 * (int64_t)o + 1], a.delta);
+            const BAEdge e = ba_edge(ba_transform(frame_T(sh, ridx, gposes, 0, of[o]), Xj), a.f, a.cx, a.cy,
+                                     px[2 * (int64_t)o], px[2 * (int64_t)o + 1], a.delta);
             a.obs_chi2[obase + o] = e.e2;
         }
     }
-    if (tid < F && sh.ridx[tid] >= 0)
-        for (int k = 0; k < 7; ++k) gposes[7 * tid + k] = sh.pose[0][tid][k];
+    if (tid < nfree)
+        for (int k = 0; k < 7; ++k) gposes[7 * sh.fre[tid] + k] = sh.pose[0][tid][k];
     if (tid == 0) {
         a.final_chi[p] = cur;
         a.iterations[p] = iters;

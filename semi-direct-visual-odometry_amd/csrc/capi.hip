@@ -1789,23 +1789,28 @@ int svo_bundle_adjust(svo_ctx* c, const svo_camera* cam, int32_t n_problems, con
     // layout: every point's observation block, checked before anything reaches the device
     std::vector<int32_t> pobs(NX + 1, 0);
     std::vector<int64_t> tab_off(NP + 1, 0);
+    std::vector<int32_t> ridx(NF, -1), seen;
     int32_t max_points = 0;
     for (size_t p = 0; p < NP; ++p) {
         const int32_t F = frame_off[p + 1] - frame_off[p], P = point_off[p + 1] - point_off[p];
-        if (F > SVO_BA_MAX_FRAMES)
-            return fail(SVO_ERR_ARG, "svo_bundle_adjust: problem %zu has %d frames (at most %d)", p, F, SVO_BA_MAX_FRAMES);
+        int32_t nfree = 0;  // only the free frames enter the reduced system, which lives in LDS
+        for (int32_t i = 0; i < F; ++i)
+            if (!frame_fixed[frame_off[p] + i]) ridx[(size_t)frame_off[p] + i] = nfree++;
+        if (nfree > SVO_BA_MAX_FRAMES)
+            return fail(SVO_ERR_ARG, "svo_bundle_adjust: problem %zu has %d frames free to move (at most %d; fixed "
+                                     "frames do not count)", p, nfree, SVO_BA_MAX_FRAMES);
+        seen.assign((size_t)F, -1);  // the last point seen in each frame
         tab_off[p + 1] = tab_off[p] + (int64_t)F * P;
         max_points = std::max(max_points, P);
         int32_t o = obs_off[p];
         for (int32_t j = 0; j < P; ++j) {
             pobs[(size_t)point_off[p] + j] = o;
-            uint32_t seen = 0;
             while (o < obs_off[p + 1] && obs_point[o] == j) {
                 const int32_t i = obs_frame[o];
                 if (i < 0 || i >= F) return fail(SVO_ERR_ARG, "svo_bundle_adjust: observation %d: frame index out of range", o);
-                if (seen & (1u << i))
+                if (seen[(size_t)i] == j)
                     return fail(SVO_ERR_ARG, "svo_bundle_adjust: observation %d: duplicate (frame, point)", o);
-                seen |= 1u << i;
+                seen[(size_t)i] = j;
                 ++o;
             }
             if (o - pobs[(size_t)point_off[p] + j] < 2)
@@ -1824,7 +1829,7 @@ int svo_bundle_adjust(svo_ctx* c, const svo_camera* cam, int32_t n_problems, con
     Carve cv;
     const size_t o_fo = cv.take((NP + 1) * 4), o_po = cv.take((NP + 1) * 4), o_oo = cv.take((NP + 1) * 4),
                  o_pobs = cv.take((NX + 1) * 4), o_to = cv.take((NP + 1) * 8), o_pose = cv.take(NF * 56),
-                 o_fix = cv.take(NF), o_pts = cv.take(NX * 24), o_of = cv.take(NO * 4), o_px = cv.take(NO * 16),
+                 o_ridx = cv.take(NF * 4), o_pts = cv.take(NX * 24), o_of = cv.take(NO * 4), o_px = cv.take(NO * 16),
                  o_tab = cv.take((size_t)tab_off[NP] * 4), o_edge = cv.take(NO * 120), o_W = cv.take(NO * 144),
                  o_Vg = cv.take(NX * 72), o_Vi = cv.take(NX * 48), o_dx = cv.take(NX * 24), o_Xt = cv.take(NX * 24),
                  o_chi2 = cv.take(NO * 8), o_ic = cv.take(NP * 8), o_fc = cv.take(NP * 8), o_it = cv.take(NP * 4),
@@ -1836,7 +1841,8 @@ int svo_bundle_adjust(svo_ctx* c, const svo_camera* cam, int32_t n_problems, con
     struct Piece { size_t off; const void* src; size_t bytes; };
     const Piece in[] = {{o_fo, frame_off, (NP + 1) * 4}, {o_po, point_off, (NP + 1) * 4}, {o_oo, obs_off, (NP + 1) * 4},
                         {o_pobs, pobs.data(), (NX + 1) * 4}, {o_to, tab_off.data(), (NP + 1) * 8},
-                        {o_pose, poses_inout, NF * 56}, {o_fix, frame_fixed, NF}, {o_pts, points_inout, NX * 24},
+                        {o_pose, poses_inout, NF * 56}, {o_ridx, ridx.data(), NF * 4},
+                        {o_pts, points_inout, NX * 24},
                         {o_of, obs_frame, NO * 4}, {o_px, obs_px, NO * 16}};
     for (const Piece& pc : in)
         if (e == hipSuccess) e = stage_copy(c, db + pc.off, pc.src, pc.bytes, hipMemcpyHostToDevice, s);
@@ -1847,7 +1853,7 @@ int svo_bundle_adjust(svo_ctx* c, const svo_camera* cam, int32_t n_problems, con
     a.pobs_off = reinterpret_cast<int32_t*>(db + o_pobs);
     a.tab_off = reinterpret_cast<int64_t*>(db + o_to);
     a.poses = reinterpret_cast<double*>(db + o_pose);
-    a.frame_fixed = reinterpret_cast<uint8_t*>(db + o_fix);
+    a.ridx = reinterpret_cast<int32_t*>(db + o_ridx);
     a.points = reinterpret_cast<double*>(db + o_pts);
     a.obs_frame = reinterpret_cast<int32_t*>(db + o_of);
     a.obs_px = reinterpret_cast<double*>(db + o_px);

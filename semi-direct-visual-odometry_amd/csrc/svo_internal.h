@@ -230,7 +230,7 @@ struct BundleAdjustArgs {  // windowed bundle adjustment over a batch of problem
     const int32_t* pobs_off;    // [n_points + 1] first observation (global index) of every point (global index)
     const int64_t* tab_off;     // [n_problems + 1] start of each problem's frames x points table in `tab`
     double* poses;              // [n_frames][7] in/out
-    const uint8_t* frame_fixed; // [n_frames]
+    const int32_t* ridx;        // [n_frames] reduced index of a free frame within its problem, -1 for a fixed frame
     double* points;             // [n_points][3] in/out
     const int32_t* obs_frame;   // [n_obs] local frame index
     const double* obs_px;       // [n_obs][2]

@@ -3,7 +3,9 @@
 #include "svo.hpp"
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
+#include <limits>
 #include <iomanip>
 #include <random>
 #include <string>
@@ -218,6 +220,7 @@ double BundleAdjustment::optimizePose(std::shared_ptr<Frame>& frame) {
 
 // ------------------------------------------------------------------ DepthEstimator
 void DepthEstimator::addKeyframe(const std::shared_ptr<Frame>& frame, double depthMean, double depthMin) {
+    dropDeletedKeyframe();
     const int32_t kf = (int32_t)m_keyframes.size();
     m_keyframes.push_back(frame);
     for (const auto& f : frame->m_features) {
@@ -442,7 +445,8 @@ BundleAdjustment::WindowResult BundleAdjustment::adjust(const std::vector<Frame*
                                                         const std::vector<std::shared_ptr<Point>>& points,
                                                         std::vector<Edge>& edges, double reprojectionError,
                                                         int32_t structureIterations) {
-    if (frames.size() > SVO_BA_MAX_FRAMES) throw Error(SVO_ERR_ARG, "svo: bundle adjustment over more than 16 frames");
+    if (frames.size() - (std::size_t)std::count_if(fixed.begin(), fixed.end(), [](uint8_t f) { return f != 0; }) > SVO_BA_MAX_FRAMES)
+        throw Error(SVO_ERR_ARG, "svo: bundle adjustment over more than 16 frames free to move");
     const int32_t frameOff[2] = {0, (int32_t)frames.size()}, pointOff[2] = {0, (int32_t)points.size()},
                   obsOff[2] = {0, (int32_t)edges.size()};
     std::vector<double> poses(7 * frames.size()), pos(3 * points.size()), px(2 * edges.size()), chi2(edges.size());
@@ -634,6 +638,359 @@ bool algorithm::computeEssentialMatrix(Context& ctx, std::shared_ptr<Frame>& ref
     }
     return refFrame->numberObservation() > thresholdCorrespondingPoints &&
            curFrame->numberObservation() > thresholdCorrespondingPoints;  // (:166-170)
+}
+
+// ------------------------------------------------------------------ pose algebra, Frame helpers (System's host side)
+// The operation order below is the Python mirror's (core.py _quat_rotate / _quat_mul / pose_compose / pose_inverse):
+// with -ffp-contract=off both mirrors form the same bits.
+static Vec3 cross3(const double* a, const Vec3& b) {
+    return {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
+}
+static Vec3 quatRotate(const double* q, const Vec3& v) {  // Eigen's _transformVector
+    Vec3 u = cross3(q, v);
+    for (double& x : u) x = x + x;
+    const Vec3 c = cross3(q, u);
+    return {(v[0] + q[3] * u[0]) + c[0], (v[1] + q[3] * u[1]) + c[1], (v[2] + q[3] * u[2]) + c[2]};
+}
+static double norm3(const Vec3& d) { return std::sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]); }
+
+Pose poseInverse(const Pose& p) {
+    const double qi[4] = {p[0] * -1.0, p[1] * -1.0, p[2] * -1.0, p[3] * 1.0};
+    const Vec3 t = quatRotate(qi, {p[4], p[5], p[6]});
+    return {qi[0], qi[1], qi[2], qi[3], -t[0], -t[1], -t[2]};
+}
+
+Pose poseCompose(const Pose& a, const Pose& b) {
+    const double ax = a[0], ay = a[1], az = a[2], aw = a[3], bx = b[0], by = b[1], bz = b[2], bw = b[3];
+    const double q[4] = {aw * bx + ax * bw + ay * bz - az * by, aw * by + ay * bw + az * bx - ax * bz,
+                         aw * bz + az * bw + ax * by - ay * bx, aw * bw - ax * bx - ay * by - az * bz};
+    const double n = std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+    const Vec3 t = quatRotate(a.data(), {b[4], b[5], b[6]});
+    return {q[0] / n, q[1] / n, q[2] / n, q[3] / n, a[4] + t[0], a[5] + t[1], a[6] + t[2]};
+}
+
+uint32_t Frame::numberObservationWithPoints() const {
+    uint32_t n = 0;
+    for (const auto& f : m_features) n += f->m_point != nullptr;
+    return n;
+}
+Vec3 Frame::world2camera(const Vec3& p) const {
+    const Vec3 r = quatRotate(m_absPose.data(), p);
+    return {r[0] + m_absPose[4], r[1] + m_absPose[5], r[2] + m_absPose[6]};
+}
+Vec3 Frame::cameraInWorld() const {
+    const double qi[4] = {m_absPose[0] * -1.0, m_absPose[1] * -1.0, m_absPose[2] * -1.0, m_absPose[3] * 1.0};
+    const Vec3 r = quatRotate(qi, {m_absPose[4], m_absPose[5], m_absPose[6]});
+    return {-r[0], -r[1], -r[2]};
+}
+bool Frame::isVisible(const Vec3& p) const {
+    const Vec3 c = world2camera(p);
+    if (c[2] < 0.0) return false;
+    return m_camera->isInFrame(m_camera->project2d(c));
+}
+
+Pose algorithm::computeRelativePose(const std::shared_ptr<Frame>& refFrame, const std::shared_ptr<Frame>& curFrame) {
+    return poseCompose(curFrame->m_absPose, poseInverse(refFrame->m_absPose));
+}
+void algorithm::normalizedDepthCamera(const std::shared_ptr<Frame>& frame, std::vector<double>& out) {
+    out.resize(frame->numberObservation());
+    for (std::size_t i = 0; i < out.size(); ++i) {
+        if (!frame->m_features[i]->m_point) throw Error(SVO_ERR_ARG, "svo: normalizedDepthCamera: a feature without a point");
+        out[i] = norm3(frame->world2camera(frame->m_features[i]->m_point->m_position));
+    }
+}
+double algorithm::computeMedian(const std::vector<double>& input) {
+    std::vector<double> vec(input);
+    if (vec.empty()) return std::nan("");
+    const auto middleSize = vec.size() / 2;
+    std::nth_element(vec.begin(), vec.begin() + (std::ptrdiff_t)middleSize, vec.end());
+    return vec.size() % 2 != 0 ? vec[middleSize] : (vec[middleSize - 1] + vec[middleSize]) / 2.0;
+}
+uint32_t algorithm::computeNumberProjectedPoints(const std::shared_ptr<Frame>& curFrame) {
+    const Pose rel = computeRelativePose(curFrame->m_lastKeyframe, curFrame);
+    const Vec3 C = curFrame->cameraInWorld();
+    uint32_t cnt = 0;
+    for (const auto& f : curFrame->m_features) {
+        if (!f->m_point) continue;
+        const Vec3& X = f->m_point->m_position;
+        const double depthNorm = norm3({X[0] - C[0], X[1] - C[1], X[2] - C[2]});
+        const Vec3 r = quatRotate(rel.data(), {f->m_bearingVec[0] * depthNorm, f->m_bearingVec[1] * depthNorm,
+                                               f->m_bearingVec[2] * depthNorm});
+        if (curFrame->m_camera->isInFrame(curFrame->m_camera->project2d({r[0] + rel[4], r[1] + rel[5], r[2] + rel[6]}), 5.0))
+            ++cnt;
+    }
+    return cnt;
+}
+
+// ------------------------------------------------------------------ Map: keyframes
+void Map::getCloseKeyframes(const std::shared_ptr<Frame>& frame,
+                            std::vector<std::pair<std::shared_ptr<Frame>, double>>& closeKeyframes) const {
+    for (auto it = m_keyFrames.rbegin(); it != m_keyFrames.rend(); ++it) {
+        const auto& keyFrame = *it;
+        if (keyFrame == frame) continue;
+        for (const auto& feature : keyFrame->m_features) {
+            if (!feature->m_point || !frame->isVisible(feature->m_point->m_position)) continue;
+            closeKeyframes.emplace_back(keyFrame, norm3({frame->m_absPose[4] - keyFrame->m_absPose[4],
+                                                         frame->m_absPose[5] - keyFrame->m_absPose[5],
+                                                         frame->m_absPose[6] - keyFrame->m_absPose[6]}));
+            break;
+        }
+    }
+}
+void Map::getClosestKeyframe(const std::shared_ptr<Frame>& frame, std::shared_ptr<Frame>& closestKeyframe) const {
+    std::vector<std::pair<std::shared_ptr<Frame>, double>> close;
+    getCloseKeyframes(frame, close);
+    closestKeyframe = nullptr;
+    double minDistance = std::numeric_limits<double>::max();
+    for (const auto& e : close)
+        if (e.first != frame && e.second < minDistance) {
+            minDistance = e.second;
+            closestKeyframe = e.first;
+        }
+}
+void Map::getFurthestKeyframe(const Vec3& pos, std::shared_ptr<Frame>& furthestKeyframe) const {
+    double maxDistance = 0.0;
+    for (const auto& frame : m_keyFrames) {
+        const Vec3 c = frame->cameraInWorld();
+        const double dist = norm3({c[0] - pos[0], c[1] - pos[1], c[2] - pos[2]});
+        if (dist > maxDistance) {
+            maxDistance = dist;
+            furthestKeyframe = frame;
+        }
+    }
+}
+void Map::removeFrame(const std::shared_ptr<Frame>& frame) {
+    const auto it = std::find(m_keyFrames.begin(), m_keyFrames.end(), frame);
+    if (it == m_keyFrames.end()) throw Error(SVO_ERR_ARG, "svo: removeFrame: not a keyframe of this map");
+    for (auto& feature : frame->m_features)
+        if (feature->m_point) {
+            feature->m_point->removeFrame(feature->m_frame);
+            feature->m_point = nullptr;
+        }
+    frame->m_features.clear();
+    frame->m_lastKeyframe = nullptr;
+    m_keyFrames.erase(it);
+    m_candidates.erase(std::remove_if(m_candidates.begin(), m_candidates.end(),
+                                      [&](const Candidate& c) { return c.feature->m_frame == frame.get(); }),
+                       m_candidates.end());
+}
+
+// ------------------------------------------------------------------ DepthEstimator: frames in, keyframes out
+void DepthEstimator::reset() {
+    m_keyframes.clear();
+    m_features.clear();
+    m_seeds.clear();
+    m_deletedKeyframe = nullptr;
+}
+void DepthEstimator::dropDeletedKeyframe() {
+    const std::shared_ptr<Frame> frame = std::move(m_deletedKeyframe);
+    m_deletedKeyframe = nullptr;
+    if (!frame) return;
+    std::vector<int32_t> remap(m_keyframes.size(), -1);
+    std::vector<std::shared_ptr<Frame>> kept;
+    for (std::size_t k = 0; k < m_keyframes.size(); ++k)
+        if (m_keyframes[k] != frame) {
+            remap[k] = (int32_t)kept.size();
+            kept.push_back(m_keyframes[k]);
+        }
+    std::vector<std::shared_ptr<Feature>> features;
+    std::vector<svo_depth_seed> seeds;
+    for (std::size_t i = 0; i < m_seeds.size(); ++i)
+        if (m_features[i]->m_frame != frame.get()) {
+            features.push_back(m_features[i]);
+            seeds.push_back(m_seeds[i]);
+            seeds.back().kf = remap[(std::size_t)m_seeds[i].kf];
+        }
+    m_keyframes.swap(kept);
+    m_features.swap(features);
+    m_seeds.swap(seeds);
+}
+void DepthEstimator::addFrame(const std::shared_ptr<Frame>& frame) {
+    dropDeletedKeyframe();
+    for (auto& c : updateFilters(frame))
+        if (m_map) m_map->addNewCandidate(c.first, c.second);
+}
+
+// ------------------------------------------------------------------ System
+System::System(Context& ctx, const Config& c)
+    : m_ctx(ctx), m_config(c),
+      m_camera(std::make_shared<PinholeCamera>(PinholeCamera{c.m_imgWidth, c.m_imgHeight, c.m_fx, c.m_fy, c.m_cx, c.m_cy})),
+      m_alignment(ctx, c.m_patchSizeImageAlignment, c.m_minLevelImagePyramid, c.m_maxLevelImagePyramid, 6, c.m_medianMode),
+      m_featureSelector(ctx, c.m_imgWidth, c.m_imgHeight, c.m_cellPixelSize),
+      m_map(ctx, m_camera, c.m_cellPixelSize, c.m_mapCellSeed), m_depthEstimator(ctx, &m_map),
+      m_bundler(ctx, m_camera, 0, 6) {}
+
+template <class F> void System::timed(const char* name, F&& fn) {
+    if (!m_instrument) {
+        fn();
+        return;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    fn();
+    m_timings[name] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
+
+template <class F> void System::runBA(const std::vector<std::shared_ptr<Frame>>& frames, F&& fn) {
+    if (!m_instrument) {
+        fn();
+        return;
+    }
+    std::vector<std::vector<std::shared_ptr<Feature>>> before;
+    for (const auto& fr : frames) before.push_back(fr->m_features);
+    timed("ba", fn);
+    for (std::size_t k = 0; k < frames.size(); ++k)
+        for (std::size_t i = 0; i < before[k].size(); ++i)
+            if (std::find(frames[k]->m_features.begin(), frames[k]->m_features.end(), before[k][i]) == frames[k]->m_features.end())
+                m_baRemoved.emplace_back(frames[k]->m_id, i);
+}
+
+bool System::addImage(const uint8_t* img, uint64_t timestamp) {
+    if (m_instrument) {
+        m_timings.clear();
+        m_baRemoved.clear();
+    }
+    timed("frame", [&] {
+        m_curFrame = std::make_shared<Frame>(m_ctx, m_camera, img, (uint32_t)m_config.m_maxLevelImagePyramid + 1, m_activeKeyframe);
+    });
+    m_curFrame->m_timestamp = timestamp;
+    m_allFrames.push_back(m_curFrame);
+    Result res = Result::Failed;
+    if (m_systemStatus == Status::Procese_New_Frame) res = processNewFrame();
+    else if (m_systemStatus == Status::Process_Second_Frame) res = processSecondFrame();
+    else if (m_systemStatus == Status::Process_First_Frame) res = processFirstFrame();
+    else if (m_systemStatus == Status::Process_Relocalization) {
+        std::shared_ptr<Frame> closestKeyframe;
+        m_map.getClosestKeyframe(m_curFrame, closestKeyframe);
+        res = relocalizeFrame(closestKeyframe);
+    }
+    if (m_refFrame != nullptr) m_predictionRelativePose = algorithm::computeRelativePose(m_refFrame, m_curFrame);
+    m_lastResult = res;
+    if (res == Result::Failed) return false;
+    m_refFrame = m_curFrame;
+    return true;
+}
+
+void System::select(std::shared_ptr<Frame>& frame) {
+    timed("select", [&] {
+        m_featureSelector.gradientMagnitudeWithSSC(frame, m_config.m_thresholdGradientMagnitude,
+                                                   m_config.m_desiredDetectedPointsForInitialization, true);
+    });
+}
+
+System::Result System::processFirstFrame() {
+    select(m_curFrame);
+    if (m_curFrame->numberObservation() < m_config.m_minDetectedPointsSuccessInitialization) return Result::Failed;
+    m_curFrame->setKeyframe();
+    m_activeKeyframe = m_curFrame;
+    m_map.addKeyframe(m_curFrame);
+    m_systemStatus = Status::Process_Second_Frame;
+    return Result::Success;
+}
+
+System::Result System::processSecondFrame() {
+    bool ok = false;
+    timed("klt", [&] {
+        ok = algorithm::computeOpticalFlowSparse(m_ctx, m_refFrame, m_curFrame, m_config.m_patchSizeOpticalFlow,
+                                                 m_config.m_disparityThreshold);
+    });
+    if (!ok) return Result::Failed;
+    const uint32_t thresholdCorrespondingPoints = m_config.m_minDetectedPointsSuccessInitialization * 0.5;
+    std::array<double, 9> E{};
+    timed("essential", [&] {
+        ok = algorithm::computeEssentialMatrix(m_ctx, m_refFrame, m_curFrame, 1.0, thresholdCorrespondingPoints, E,
+                                               m_config.m_ransacSeed);
+    });
+    if (!ok) return Result::Failed;
+    timed("two_view", [&] {
+        ok = initializeTwoView(m_ctx, m_refFrame, m_curFrame, E, m_config.m_initMapScaleFactor, m_config.m_cellPixelSize).ok;
+    });
+    if (!ok) return Result::Failed;
+    runBA({m_refFrame, m_curFrame}, [&] { m_bundler.twoViewBA(m_refFrame, m_curFrame, 2.0); });
+    m_curFrame->setKeyframe();
+    m_activeKeyframe = m_curFrame;
+    std::vector<double> depths;
+    algorithm::normalizedDepthCamera(m_curFrame, depths);
+    const double medianDepth = algorithm::computeMedian(depths);
+    const double minDepth = *std::min_element(depths.begin(), depths.end());
+    m_featureSelector.setExistingFeatures(m_curFrame->m_features);
+    select(m_curFrame);
+    m_depthEstimator.addKeyframe(m_curFrame, medianDepth, 0.5 * minDepth);
+    m_map.addKeyframe(m_curFrame);
+    m_systemStatus = Status::Procese_New_Frame;
+    return Result::Success;
+}
+
+System::Result System::processNewFrame() {
+    m_curFrame->m_absPose = poseCompose(m_predictionRelativePose, m_refFrame->m_absPose);
+    timed("align", [&] { m_alignment.align(m_refFrame, m_curFrame); });
+    std::vector<std::pair<std::shared_ptr<Frame>, int32_t>> overlapKeyFrames;
+    timed("reproject", [&] { m_map.reprojectMap(m_refFrame, m_curFrame, overlapKeyFrames); });
+    timed("candidates", [&] { m_map.addCandidateToFrame(m_curFrame); });
+    if (!computeTrackingQuality(m_curFrame, m_refFrame->numberObservationWithPoints())) {
+        m_curFrame->m_absPose = m_refFrame->m_absPose;
+        return Result::Success;
+    }
+    std::vector<double> depths;
+    algorithm::normalizedDepthCamera(m_curFrame, depths);
+    const double depthMean = algorithm::computeMedian(depths);
+    const double depthMin = *std::min_element(depths.begin(), depths.end());
+    if (needKeyframe()) {
+        timed("depth", [&] { m_depthEstimator.addFrame(m_curFrame); });
+        return Result::Success;
+    }
+    m_curFrame->setKeyframe();
+    m_map.addKeyframe(m_curFrame);
+    m_activeKeyframe = m_curFrame;
+    runBA(m_map.m_keyFrames, [&] { m_bundler.localBA(m_map.m_keyFrames, 2.0); });
+    m_featureSelector.setExistingFeatures(m_curFrame->m_features);
+    select(m_curFrame);
+    m_depthEstimator.addKeyframe(m_curFrame, depthMean, depthMin * 0.5);
+    if (m_map.sizeKeyframes() > m_config.m_maxKeyframes) {  // :436-442
+        std::shared_ptr<Frame> furthestFrame;
+        m_map.getFurthestKeyframe(m_curFrame->cameraInWorld(), furthestFrame);
+        m_depthEstimator.removeKeyframe(furthestFrame);
+        m_map.removeFrame(furthestFrame);
+    }
+    return Result::Keyframe;
+}
+
+System::Result System::relocalizeFrame(std::shared_ptr<Frame>& closestKeyframe) {
+    if (closestKeyframe == nullptr) return Result::Failed;
+    if (!closestKeyframe->m_lastKeyframe)  // (the reference dereferences the null pointer in ImageAlignment::align)
+        throw Error(SVO_ERR_ARG, "svo: relocalisation against a keyframe without a last keyframe");
+    timed("align", [&] { m_alignment.align(closestKeyframe, m_curFrame); });
+    return Result::Success;
+}
+
+bool System::computeTrackingQuality(const std::shared_ptr<Frame>& frame, uint32_t refFrameNumberObservations) const {
+    const int32_t curNumberObservations = (int32_t)frame->numberObservation();
+    if (frame->numberObservation() < 50) return false;
+    return !((int32_t)refFrameNumberObservations - curNumberObservations > 40);
+}
+
+bool System::needKeyframe() const {  // (the other quantities of :485-501 only feed the reference's log)
+    return m_curFrame->m_id - m_curFrame->m_lastKeyframe->m_id < 3;
+}
+
+System::Summary System::reportSummary() const {
+    Summary s;
+    std::vector<const Frame*> frames;
+    for (const auto& k : m_map.m_keyFrames) frames.push_back(k.get());
+    for (const auto* fr : {m_refFrame.get(), m_curFrame.get()})
+        if (fr && std::find(frames.begin(), frames.end(), fr) == frames.end()) frames.push_back(fr);
+    std::vector<const Point*> points;
+    for (const auto* fr : frames) {
+        s.features += fr->numberObservation();
+        for (const auto& f : fr->m_features)
+            if (f->m_point && std::find(points.begin(), points.end(), f->m_point.get()) == points.end())
+                points.push_back(f->m_point.get());
+    }
+    s.frames = frames.size();
+    s.points = points.size();
+    s.filters = m_depthEstimator.numberFilters();
+    s.candidates = m_map.m_candidates.size();
+    s.keyframes = m_map.sizeKeyframes();
+    return s;
 }
 
 // ------------------------------------------------------------------ trajectory / feature dump

@@ -39,6 +39,16 @@
 //                                  ref then the cur image (W x H bytes each); PX.bin: N x px[2] doubles, the ref
 //                                  frame's features; prints "klt result n_ref n_cur", then with %a "ref x y" per
 //                                  feature left in the ref frame and "cur x y" per feature of the cur frame
+//   svo_host_check system DATA.bin IMAGES.raw   System::addImage over a sequence (GPU); DATA.bin (doubles): fx fy cx cy
+//                                  W H, cell, desired points, min points, disparity threshold, map scale, ransac
+//                                  seed, max keyframes, patch (optical flow), patch (alignment), min level, max
+//                                  level, gradient threshold, median mode, n_frames, relocalise (1: the status is set
+//                                  to relocalisation before the last frame), n_cells, the map's cell order;
+//                                  IMAGES.raw: the frames, W x H bytes each; prints per frame "frame k result status
+//                                  keyframe n_obs n_obs_points seeds candidates keyframes", "pose" + the cur pose[7]
+//                                  with %a, "removed" + frame:index of the features the BA removed (frame ids
+//                                  relative to the first), "time" + step=seconds, and last the trajectory lines; an
+//                                  optional PASSES argument repeats the whole run on a fresh System (timing)
 #include <algorithm>
 #include <array>
 #include <chrono>
@@ -48,6 +58,7 @@
 #include <iostream>
 #include <iterator>
 #include <memory>
+#include <sstream>
 #include <string>
 #include <vector>
 
@@ -471,7 +482,69 @@ int main(int argc, char** argv) {
             if (reps > 0) std::printf("ms %.6f\n", total_ms / reps);
             return 0;
         }
-        std::fprintf(stderr, "usage: svo_host_check io | fs W H CELL THR NUM BUCKET IMAGE [EX EY]... | fv W H CELL THR IMAGE | init DATA.bin | essential DATA.bin | wba DATA.bin\n");
+        if (mode == "system" && argc >= 4) {
+            std::ifstream f(argv[2], std::ios::binary);
+            std::vector<char> raw((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+            const double* d = reinterpret_cast<const double*>(raw.data());
+            const size_t nd = raw.size() / sizeof(double);
+            if (nd < 22) throw std::runtime_error("system: DATA.bin too short");
+            Config c;
+            c.m_fx = d[0]; c.m_fy = d[1]; c.m_cx = d[2]; c.m_cy = d[3];
+            c.m_imgWidth = (int32_t)d[4]; c.m_imgHeight = (int32_t)d[5];
+            c.m_cellPixelSize = (int32_t)d[6];
+            c.m_desiredDetectedPointsForInitialization = (uint32_t)d[7];
+            c.m_minDetectedPointsSuccessInitialization = (uint32_t)d[8];
+            c.m_disparityThreshold = d[9];
+            c.m_initMapScaleFactor = d[10];
+            c.m_ransacSeed = (uint64_t)d[11];
+            c.m_maxKeyframes = (size_t)d[12];
+            c.m_patchSizeOpticalFlow = (uint32_t)d[13];
+            c.m_patchSizeImageAlignment = (uint32_t)d[14];
+            c.m_minLevelImagePyramid = (int32_t)d[15];
+            c.m_maxLevelImagePyramid = (int32_t)d[16];
+            c.m_thresholdGradientMagnitude = (uint32_t)d[17];
+            c.m_medianMode = (int32_t)d[18];
+            const int nFrames = (int)d[19];
+            const bool relocalise = d[20] != 0.0;
+            const size_t nCells = (size_t)d[21];
+            if (nd != 22 + nCells) throw std::runtime_error("system: DATA.bin size mismatch");
+            std::vector<int32_t> order(nCells);
+            for (size_t i = 0; i < nCells; ++i) order[i] = (int32_t)d[22 + i];
+            const size_t frameBytes = (size_t)c.m_imgWidth * c.m_imgHeight;
+            const std::vector<uint8_t> imgs = read_raw(argv[3], frameBytes * (size_t)nFrames);
+            const int passes = argc > 4 ? std::atoi(argv[4]) : 1;
+            Context ctx(0);
+            for (int pass = 0; pass < passes; ++pass) {
+                System system(ctx, c);
+                if (nCells) system.map().setCellOrder(order);
+                system.setInstrument(true);
+                std::ostringstream trajectory;
+                uint64_t base = 0;
+                for (int k = 0; k < nFrames; ++k) {
+                    if (relocalise && k == nFrames - 1) system.setStatus(System::Status::Process_Relocalization);
+                    const auto t0 = std::chrono::steady_clock::now();
+                    system.addImage(imgs.data() + frameBytes * (size_t)k, (uint64_t)k);
+                    const double total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+                    const auto& cur = system.curFrame();
+                    if (k == 0) base = cur->m_id;
+                    std::printf("frame %d %d %d %d %zu %u %zu %zu %zu\n", k, (int)system.lastResult(), (int)system.status(),
+                                cur->isKeyframe() ? 1 : 0, cur->numberObservation(), cur->numberObservationWithPoints(),
+                                system.depthEstimator().numberFilters(), system.map().m_candidates.size(),
+                                system.map().sizeKeyframes());
+                    std::printf("pose");
+                    for (double v : cur->m_absPose) std::printf(" %a", v);
+                    std::printf("\nremoved");
+                    for (const auto& r : system.baRemoved()) std::printf(" %llu:%zu", (unsigned long long)(r.first - base), r.second);
+                    std::printf("\ntime total=%.9f", total);
+                    for (const auto& t : system.timings()) std::printf(" %s=%.9f", t.first.c_str(), t.second);
+                    std::printf("\n");
+                    if (system.refFrame()) system.writeInFile(trajectory);
+                }
+                std::printf("trajectory\n%s", trajectory.str().c_str());
+            }
+            return 0;
+        }
+        std::fprintf(stderr, "usage: svo_host_check io | fs W H CELL THR NUM BUCKET IMAGE [EX EY]... | fv W H CELL THR IMAGE | init DATA.bin | essential DATA.bin | wba DATA.bin | system DATA.bin IMAGES.raw [PASSES]\n");
         return 2;
     } catch (const std::exception& e) {
         std::fprintf(stderr, "svo_host_check: %s\n", e.what());

@@ -289,3 +289,20 @@ def write_map_problem(p, directory, cell_order):
         with open(path, "wb") as f:
             f.write(np.ascontiguousarray(img, np.uint8).tobytes())
     return paths
+
+
+def write_system_problem(config, images, cell_order, directory, relocalise=False):
+    """Files for build/svo_host_check system (the C++ mirror's System): system.bin (doubles, layout in
+    host/svo_host_check.cpp: the Config fields, the number of frames, the relocalise flag, the map's cell order) and
+    images.raw (the frames).  Returns the two paths."""
+    import os
+    c = config
+    hdr = [c.fx, c.fy, c.cx, c.cy, c.img_width, c.img_height, c.cell_pixel_size,
+           c.desired_detected_points_for_initialization, c.min_detected_points_success_initialization,
+           c.disparity_threshold, c.init_map_scale_factor, c.ransac_seed, c.max_keyframes, c.patch_size_optical_flow,
+           c.patch_size_image_alignment, c.min_level_image_pyramid, c.max_level_image_pyramid,
+           c.threshold_gradient_magnitude, c.median_mode, len(images), int(relocalise), len(cell_order)]
+    data, raw = os.path.join(str(directory), "system.bin"), os.path.join(str(directory), "images.raw")
+    np.concatenate([np.array(hdr, np.float64), np.asarray(cell_order, np.float64)]).tofile(data)
+    np.ascontiguousarray(images, np.uint8).tofile(raw)
+    return data, raw

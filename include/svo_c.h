@@ -98,7 +98,10 @@ int svo_device_count(int32_t* count);
 int svo_ctx_create(int32_t device, svo_ctx** out);
 int svo_ctx_destroy(svo_ctx* ctx);
 int svo_ctx_synchronize(svo_ctx* ctx);
-/* hipStream_t of the context (all work of the context is enqueued on it), for event timing. */
+/* hipStream_t of the context, for event timing.  The handle is joined with the side chains a batch run may have left
+ * pending only at the moment of this call: work the caller queues on a handle it kept across a later
+ * svo_align_batch_run does not wait for that run's chains.  Call svo_ctx_stream() (or svo_ctx_event_record) again
+ * after each run, or set SVO_DEFER_JOIN=0 when the stream has been handed out. */
 void* svo_ctx_stream(svo_ctx* ctx);
 const char* svo_last_error(void);
 int svo_abi_version(void);

@@ -195,6 +195,40 @@ def test_gpu_cpp_mirror_depth_estimator(problem, tmp_path):
 
 
 @pytest.mark.gpu
+def test_gpu_outcome_array_is_optional():
+    """svo_depth_update with `outcome` null (32 seeds): survivors and candidates are those of the call that asks for
+    the outcomes, bit for bit, and the oracle's."""
+    import ctypes
+    import svo_amd
+    from svo_amd._capi import check, lib, ptr
+    p = synth.make_depth_problem(n_seeds=32)
+    seeds = O.make_seeds(p.px, p.bearing, p.depth_mean, p.depth_min)
+    want = gpu_update(p.camera, p.kf_img, p.kf_pose, p.cur_img, p.cur_pose, seeds)
+    check_same(want, O.depth_update(p.camera, [p.kf_img], p.kf_pose[None], p.cur_img, p.cur_pose, seeds))
+    cam = p.camera
+    ps = svo_amd.PyramidSet(2, cam["width"], cam["height"], 1)
+    ps.upload(0, np.stack([p.kf_img, p.cur_img]))
+    ps.build()
+    s = np.zeros(len(seeds), svo_amd.DEPTH_SEED)
+    for k in FIELDS:
+        s[k] = seeds[k]
+    n = len(s)
+    sets = (ctypes.c_void_p * 1)(ps.handle.value)
+    frames, kf_pose = np.zeros(1, np.int32), np.ascontiguousarray(p.kf_pose, np.float64)
+    cur_pose = np.ascontiguousarray(p.cur_pose, np.float64)
+    pts, cs = np.zeros((n, 3)), np.zeros(n, np.int32)
+    n_out, n_cand = ctypes.c_int32(), ctypes.c_int32()
+    c_cam = svo_amd.PinholeCamera(cam["width"], cam["height"], cam["fx"], cam["fy"], cam["cx"], cam["cy"]).as_c()
+    check(lib().svo_depth_update(svo_amd.default_context().handle, ctypes.byref(c_cam), 1,
+                                 ctypes.cast(sets, ctypes.c_void_p), ptr(frames), ptr(kf_pose), ps.handle, 1,
+                                 ptr(cur_pose), n, ptr(s), ctypes.byref(n_out), None, ptr(pts), ptr(cs),
+                                 ctypes.byref(n_cand)))
+    assert n_out.value == len(want[0]) and n_cand.value == len(want[2])
+    assert s[:n_out.value].tobytes() == want[0].tobytes()
+    assert np.array_equal(pts[:n_cand.value], want[2]) and np.array_equal(cs[:n_cand.value], want[3])
+
+
+@pytest.mark.gpu
 def test_gpu_large_seed_set_pageable_staging():
     """80k seeds (10 MB of per-call data, past the context's 8 MB pinned staging block): the pageable
     staging path gives the oracle's answers."""

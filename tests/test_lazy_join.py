@@ -1,7 +1,8 @@
-"""Lazy chain joins (csrc/capi.hip svo_ctx::pending_batch): a reference-mode batch of >= 512 pairs runs as
-four chains, and back-to-back runs of that batch are ordered per chain instead of each run forking after every chain of
-the previous one; anything else that uses the context stream joins the pending chains first.  Every interleaving
-below must give each pair its scene's pose bit for bit (the oracle pins the scenes' poses, 1e-9):
+"""Lazy chain joins (csrc/capi_ctx.h svo_ctx::pending_batch, csrc/capi.hip ctx_stream / run_batch): a
+reference-mode batch of >= 512 pairs runs as four chains, and back-to-back runs of that batch are ordered per chain
+instead of each run forking after every chain of the previous one; anything else that uses the context stream joins
+the pending chains first.  Every interleaving below must give each pair its scene's pose bit for bit (the oracle pins
+the scenes' poses, 1e-9):
 
 * runs back to back, then results;
 * a run, then set_pairs with the pairs on other scenes (it overwrites the buffers the pending chains use), a run;

@@ -184,6 +184,30 @@ def test_gpu_batch_matches_oracle():
 
 
 @pytest.mark.gpu
+def test_gpu_payload_past_the_pinned_block_copies_directly():
+    """23 copies of the batch above in one call: 167 440 features, 8.5 MB of inputs and outputs, past the context's
+    8 MiB pinned block, so svo_pose_optimize copies every piece straight from and to the caller's arrays.  Frames are
+    independent, so every copy must give the staged 10-frame call's results (those are checked against the oracle
+    above) bit for bit."""
+    import svo_amd
+    specs = [(10, 50, "has"), (11, 51, "has"), (12, 2000, "has"), (13, 0, "has"), (14, 1, "has"), (15, 2, "has"),
+             (16, 3, "has"), (17, 300, "none"), (18, 777, "has"), (19, 4096, "has")]
+    off, b, P, has, vis, poses = _batch(specs)
+    vis_1, poses_1 = vis.copy(), np.ascontiguousarray(poses.copy())
+    err_1, st_1 = svo_amd.pose_optimize_batch(off, b, P, has, vis_1, poses_1)
+    T, F, n = 23, len(specs), int(off[-1])
+    assert 51 * T * n > 8 << 20  # 24 + 24 + 1 + 1 bytes in and 1 byte out per feature alone
+    off_t = np.concatenate([[0], (off[1:][None, :] + n * np.arange(T)[:, None]).ravel()]).astype(np.int32)
+    vis_t, poses_t = np.tile(vis, T), np.ascontiguousarray(np.tile(poses, (T, 1)))
+    err_t, st_t = svo_amd.pose_optimize_batch(off_t, np.tile(b, (T, 1)), np.tile(P, (T, 1)), np.tile(has, T), vis_t, poses_t)
+    for t in range(T):
+        assert np.array_equal(poses_t[t * F:(t + 1) * F], poses_1), t
+        assert np.array_equal(err_t[t * F:(t + 1) * F], err_1, equal_nan=True), t
+        assert np.array_equal(st_t[t * F:(t + 1) * F], st_1), t
+        assert np.array_equal(vis_t[t * n:(t + 1) * n], vis_1), t
+
+
+@pytest.mark.gpu
 def test_gpu_bundle_adjustment_object_sequence():
     """Two optimizePose calls on one object: NaN first (stale flags), then a real step — as the oracle."""
     import svo_amd

@@ -54,7 +54,9 @@ typedef struct svo_ctx svo_ctx;
 typedef struct svo_pyramid_set svo_pyramid_set;
 typedef struct svo_align_batch svo_align_batch;
 
-/* PinholeCamera without distortion (src/pinhole_camera.cpp:50-101; KITTI d = 0, resource/kitti.yaml). */
+/* PinholeCamera's ideal pinhole model (src/pinhole_camera.cpp:50-101; KITTI d = 0, resource/kitti.yaml).  Every entry
+ * point that takes a camera works on UNDISTORTED pixels: a lens with distortion is handled once per frame, ahead of the
+ * pyramid (svo_undistort_*, svo_pyramid_set_upload_undistort below), after which the image is this camera's. */
 typedef struct {
     double fx, fy, cx, cy;
     int32_t width, height;
@@ -579,6 +581,64 @@ int svo_essential_ransac(svo_ctx* ctx, const svo_camera* cam, int32_t n_pairs, c
                          const double* ref_px, const double* cur_px, double threshold, double confidence,
                          int32_t max_iterations, uint64_t seed, double* E, uint8_t* mask, int32_t* n_inliers,
                          int32_t* iterations, int32_t* best, int32_t* status, double* hyp_E, int32_t* hyp_count);
+
+/* ---------------------------------------------------------------- lens undistortion ahead of the pyramid
+ * Replaces PinholeCamera's undistortion: the map its constructor builds with cv::initUndistortRectifyMap(K, d, I, K,
+ * size, CV_16SC2, ..) (src/pinhole_camera.cpp:7-48) and PinholeCamera::undistortImage = cv::remap(.., INTER_LINEAR)
+ * over it (:178-184; pinned by tests/test_camera.cpp:105-130 against a recorded image).  The reference's System never
+ * calls undistortImage; here the step runs on the device between the upload and the pyramid build, so that everything
+ * behind a Frame sees the ideal pinhole svo_camera.  OpenCV is not part of the reference tree; the arithmetic below is
+ * THIS PROJECT'S CONTRACT, modelled on OpenCV's fixed-point remap.  On the one recorded OpenCV result the reference
+ * ships (1280 x 960, green channel) it differs in 47 of 1 228 800 bytes, by at most 3 grey levels, each at a pixel
+ * whose u * 32 or v * 32 lies within 0.002 of a rounding tie (tests/test_undistort.py).
+ *
+ * Inputs: the camera (fx, fy, cx, cy, width, height) and d = (k1, k2, p1, p2, k3) in OpenCV's order; the output camera
+ * matrix equals the input one.  Map, per output pixel (j, i), in IEEE double, every operation rounded once, in exactly
+ * this order (left to right, no contraction):
+ *   x = (j - cx) / fx            y = (i - cy) / fy
+ *   x2 = x*x   y2 = y*y   r2 = x2 + y2   xy2 = 2*x*y
+ *   kr = 1 + ((k3*r2 + k2)*r2 + k1)*r2
+ *   xd = x*kr + p1*xy2 + p2*(r2 + 2*x2)
+ *   yd = y*kr + p1*(r2 + 2*y2) + p2*xy2
+ *   u  = fx*xd + cx              v  = fy*yd + cy
+ *   iu = rint(u*32)   iv = rint(v*32)        (ties to even; as int32 after saturation)
+ *   X = iu >> 5   Y = iv >> 5   ax = iu & 31   ay = iv & 31      (arithmetic shift)
+ * Remap, in integers: the taps are (Y,X), (Y,X+1), (Y+1,X), (Y+1,X+1); a tap outside the image contributes 0
+ * (BORDER_CONSTANT with value 0, cv::remap's default);
+ *   out = ((32-ax)*(32-ay)*p00 + ax*(32-ay)*p01 + (32-ax)*ay*p10 + ax*ay*p11 + 512) >> 10
+ * (the fractions are multiples of 1/32, so OpenCV's 15-bit weight table is exactly a*b*32 and its sum correction never
+ * fires).  Stored map: X clamped to [-2, width], Y to [-2, height] (every position beyond gives 0 either way), which
+ * fits int16 up to 32767 x 32767; a larger camera is SVO_ERR_ARG.
+ * When to apply (the mirrors' rule): when any of the five coefficients is non-zero (the reference tests |k1| > 1e-5
+ * alone and would skip a purely tangential lens).  With all five zero nothing of this section runs.
+ *
+ * Two host helpers of the mirrors (PinholeCamera::raw_pixel / undistorted_pixel) carry points between the raw and the
+ * undistorted image in the same double arithmetic: raw_pixel(p) is the unrounded (u, v) above; undistorted_pixel(raw)
+ * inverts it by x <- (xd - tangential(x)) / kr(x), y likewise, SVO_UNDISTORT_POINT_ITERATIONS times from the distorted
+ * normalised point (xd, yd) = ((u - cx) / fx, (v - cy) / fy), with tangential = (p1*xy2 + p2*(r2 + 2*x2),
+ * p1*(r2 + 2*y2) + p2*xy2) and kr as above at the current (x, y); the result is (fx*x + cx, fy*y + cy). */
+typedef struct svo_undistort_map svo_undistort_map;
+typedef struct {
+    double k1, k2, p1, p2, k3;
+} svo_distortion;
+#define SVO_UNDISTORT_POINT_ITERATIONS 40
+/* Build the device-resident map of one camera (queued on the context stream; every later use is ordered after it). */
+int svo_undistort_map_create(svo_ctx* ctx, const svo_camera* cam, const svo_distortion* d, svo_undistort_map** out);
+int svo_undistort_map_destroy(svo_undistort_map* map);
+/* The map as OpenCV's CV_16SC2 + CV_16UC1 pair: xy height*width*2 (X, Y per pixel), frac height*width
+ * ((ay << 5) | ax).  Synchronous. */
+int svo_undistort_map_download(const svo_undistort_map* map, int16_t* xy, uint16_t* frac);
+/* PinholeCamera::undistortImage for `count` images (count*width*height bytes in, as many out).  Synchronous. */
+int svo_undistort_images(svo_ctx* ctx, const svo_undistort_map* map, const uint8_t* host_in, uint8_t* host_out,
+                         int32_t count);
+/* svo_pyramid_set_upload / _upload_device of RAW images: they are remapped into level 0 of frames
+ * [first, first+count) (the host form stages them in the context's per-call device block first).  Stream-ordered like
+ * the plain uploads, with the same waits with respect to svo_pyramid_set_build_async.  SVO_ERR_ARG when the map's size
+ * differs from the set's or the map belongs to another context. */
+int svo_pyramid_set_upload_undistort(svo_pyramid_set* set, int32_t first, int32_t count, const uint8_t* host_images,
+                                     const svo_undistort_map* map);
+int svo_pyramid_set_upload_undistort_device(svo_pyramid_set* set, int32_t first, int32_t count,
+                                            const uint8_t* dev_images, const svo_undistort_map* map);
 
 #ifdef __cplusplus
 }

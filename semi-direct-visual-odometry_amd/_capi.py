@@ -25,6 +25,10 @@ class SvoCamera(ctypes.Structure):
                 ("width", c_int32), ("height", c_int32)]
 
 
+class SvoDistortion(ctypes.Structure):
+    _fields_ = [("k1", c_double), ("k2", c_double), ("p1", c_double), ("p2", c_double), ("k3", c_double)]
+
+
 class SvoAlignParams(ctypes.Structure):
     _fields_ = [("patch_size", c_int32), ("min_level", c_int32), ("max_level", c_int32), ("median_mode", c_int32)]
 
@@ -116,6 +120,13 @@ _SIGNATURES = [
     ("svo_essential_ransac", c_int32, [c_void_p, ctypes.POINTER(SvoCamera), c_int32, c_void_p, c_void_p, c_void_p,
                                        c_double, c_double, c_int32, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("svo_undistort_map_create", c_int32, [c_void_p, ctypes.POINTER(SvoCamera), ctypes.POINTER(SvoDistortion),
+                                           ctypes.POINTER(c_void_p)]),
+    ("svo_undistort_map_destroy", c_int32, [c_void_p]),
+    ("svo_undistort_map_download", c_int32, [c_void_p, c_void_p, c_void_p]),
+    ("svo_undistort_images", c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32]),
+    ("svo_pyramid_set_upload_undistort", c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    ("svo_pyramid_set_upload_undistort_device", c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
 ]
 
 EXPORTED = [s[0] for s in _SIGNATURES]

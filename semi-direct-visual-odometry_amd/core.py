@@ -1,7 +1,8 @@
 """Python mirror of the reference's class surface for the alignment hot path, over the C ABI.
 
 Names, argument meaning and error behaviour follow the reference:
-  PinholeCamera      include/pinhole_camera.hpp:16 (undistorted path, src/pinhole_camera.cpp:50-101)
+  PinholeCamera      include/pinhole_camera.hpp:16 (the pinhole path on undistorted pixels, src/pinhole_camera.cpp:50-101;
+                     distortion is removed from the image once, ahead of the pyramid: undistort_image)
   ImagePyramid       include/image_pyramid.hpp:23-149          (device resident; getters download)
   Frame / Feature / Point   include/frame.hpp:70-208, include/feature.hpp:14, include/point.hpp:14
   ImageAlignment     include/image_alignment.hpp:15-73         (align(ref, cur) -> error, cur pose in place)
@@ -70,14 +71,118 @@ def device_count():
     return n.value
 
 
+UNDISTORT_POINT_ITERATIONS = 40  # include/svo_c.h SVO_UNDISTORT_POINT_ITERATIONS
+
+
+class UndistortMap:
+    """The device-resident fixed-point undistortion map of one camera on one context (svo_undistort_map)."""
+
+    def __init__(self, camera, ctx=None):
+        self.ctx = ctx or default_context()
+        self.width, self.height = camera.width, camera.height
+        h = ctypes.c_void_p()
+        cam, d = camera.as_c(), _capi.SvoDistortion(*camera.d)
+        check(lib().svo_undistort_map_create(self.ctx.handle, ctypes.byref(cam), ctypes.byref(d), ctypes.byref(h)))
+        self.handle = h
+
+    def download(self):
+        """(xy (h, w, 2) int16: X, Y; frac (h, w) uint16: ay << 5 | ax), OpenCV's CV_16SC2 + CV_16UC1 pair."""
+        xy = np.empty((self.height, self.width, 2), np.int16)
+        frac = np.empty((self.height, self.width), np.uint16)
+        check(lib().svo_undistort_map_download(self.handle, ptr(xy), ptr(frac)))
+        return xy, frac
+
+    def undistort(self, images):
+        """PinholeCamera::undistortImage for one (h, w) image or a (count, h, w) stack (svo_undistort_images)."""
+        imgs = np.ascontiguousarray(images, dtype=np.uint8)
+        if imgs.ndim not in (2, 3) or imgs.shape[-2:] != (self.height, self.width):
+            raise ValueError(f"image shape {imgs.shape} does not end in ({self.height}, {self.width})")
+        out = np.empty_like(imgs)
+        count = imgs.shape[0] if imgs.ndim == 3 else 1
+        check(lib().svo_undistort_images(self.ctx.handle, self.handle, ptr(imgs), ptr(out), count))
+        return out
+
+    def close(self):
+        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
+            lib().svo_undistort_map_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class PinholeCamera:
-    def __init__(self, width, height, fx, fy, cx, cy):
+    """PinholeCamera(width, height, fx, fy, cx, cy, d0..d4) (include/pinhole_camera.hpp:16).  d = (k1, k2, p1, p2, k3)
+    in OpenCV's order describes the RAW image; it is consumed once per frame, ahead of the pyramid (undistort_image,
+    PyramidSet.upload(camera=...), Frame).  project2d, inverse_project2d, is_in_frame and as_c are the plain pinhole
+    and operate on UNDISTORTED pixels, whatever d is: the reference's distorted project2d (src/pinhole_camera.cpp:58-72)
+    is wrong upstream and never meets an undistorted image, and is not mirrored.  raw_pixel / undistorted_pixel carry a
+    point between the two images."""
+
+    def __init__(self, width, height, fx, fy, cx, cy, d0=0.0, d1=0.0, d2=0.0, d3=0.0, d4=0.0):
         self.width, self.height = int(width), int(height)
         self.fx, self.fy, self.cx, self.cy = float(fx), float(fy), float(cx), float(cy)
+        self.d = (float(d0), float(d1), float(d2), float(d3), float(d4))
+        self._maps = {}  # context -> UndistortMap, created on first use
 
     @classmethod
     def kitti(cls):  # resource/kitti.yaml:7-8, config/config.json:10-11
         return cls(1241, 376, 721.5377, 721.5377, 609.5593, 172.8540)
+
+    @property
+    def apply_distortion(self):
+        """Any coefficient non-zero (the reference tests |d0| > 1e-5 alone: a deliberate difference, include/svo_c.h)."""
+        return any(v != 0.0 for v in self.d)
+
+    def undistort_map(self, ctx=None):
+        ctx = ctx or default_context()
+        m = self._maps.get(ctx)
+        if m is None or not m.handle:
+            m = self._maps[ctx] = UndistortMap(self, ctx)
+        return m
+
+    def undistort_image(self, img, ctx=None):  # src/pinhole_camera.cpp:178-184 (a copy when nothing applies, :183)
+        if not self.apply_distortion:
+            return np.array(img, dtype=np.uint8, copy=True)
+        return self.undistort_map(ctx).undistort(img)
+
+    def _distort(self, x, y):  # (kr, tangential x, tangential y) at a normalised point
+        k1, k2, p1, p2, k3 = self.d
+        x2 = x * x
+        y2 = y * y
+        r2 = x2 + y2
+        xy2 = (2.0 * x) * y
+        kr = 1.0 + ((k3 * r2 + k2) * r2 + k1) * r2
+        return kr, p1 * xy2 + p2 * (r2 + 2.0 * x2), p1 * (r2 + 2.0 * y2) + p2 * xy2
+
+    def raw_pixel(self, p):
+        """Where the undistorted pixel p = (j, i) lies in the raw image: the unrounded (u, v) of the map contract."""
+        k1, k2, p1, p2, k3 = self.d
+        x = (float(p[0]) - self.cx) / self.fx
+        y = (float(p[1]) - self.cy) / self.fy
+        x2 = x * x
+        y2 = y * y
+        r2 = x2 + y2
+        xy2 = (2.0 * x) * y
+        kr = 1.0 + ((k3 * r2 + k2) * r2 + k1) * r2
+        xd = (x * kr + p1 * xy2) + p2 * (r2 + 2.0 * x2)  # the contract's order, left to right
+        yd = (y * kr + p1 * (r2 + 2.0 * y2)) + p2 * xy2
+        return np.array([self.fx * xd + self.cx, self.fy * yd + self.cy])
+
+    def undistorted_pixel(self, raw):
+        """The inverse of raw_pixel: x <- (xd - tangential(x)) / kr(x), UNDISTORT_POINT_ITERATIONS times from the
+        distorted normalised point."""
+        xd = (float(raw[0]) - self.cx) / self.fx
+        yd = (float(raw[1]) - self.cy) / self.fy
+        x, y = xd, yd
+        for _ in range(UNDISTORT_POINT_ITERATIONS):
+            kr, tx, ty = self._distort(x, y)
+            x = (xd - tx) / kr
+            y = (yd - ty) / kr
+        return np.array([self.fx * x + self.cx, self.fy * y + self.cy])
 
     def as_c(self):
         return _capi.SvoCamera(self.fx, self.fy, self.cx, self.cy, self.width, self.height)
@@ -107,13 +212,30 @@ class PyramidSet:
                                            ctypes.byref(h)))
         self.handle = h
 
-    def upload(self, first, images):
+    def upload(self, first, images, camera=None):
+        """Level 0 of frames [first, first + count).  With a camera that applies distortion the images are RAW: they
+        are undistorted on the device on their way in (svo_pyramid_set_upload_undistort)."""
         imgs = np.ascontiguousarray(images, dtype=np.uint8)
         count = imgs.shape[0] if imgs.ndim == 3 else 1
         if imgs.shape[-2:] != (self.height, self.width):
             raise ValueError(f"image shape {imgs.shape[-2:]} != ({self.height}, {self.width})")
-        check(lib().svo_pyramid_set_upload(self.handle, int(first), count, ptr(imgs)))
+        if camera is not None and camera.apply_distortion:
+            check(lib().svo_pyramid_set_upload_undistort(self.handle, int(first), count, ptr(imgs),
+                                                         camera.undistort_map(self.ctx).handle))
+        else:
+            check(lib().svo_pyramid_set_upload(self.handle, int(first), count, ptr(imgs)))
         self.ctx.synchronize()  # the host buffer may die after return
+
+    def upload_device(self, first, count, dev_ptr, camera=None):
+        """upload() from device memory (count tightly packed images at the address dev_ptr), stream-ordered: the
+        memory must stay untouched until the context stream has passed the copy (svo_pyramid_set_upload_device, or
+        svo_pyramid_set_upload_undistort_device with a camera that applies distortion)."""
+        src = ctypes.c_void_p(int(dev_ptr))
+        if camera is not None and camera.apply_distortion:
+            check(lib().svo_pyramid_set_upload_undistort_device(self.handle, int(first), int(count), src,
+                                                                camera.undistort_map(self.ctx).handle))
+        else:
+            check(lib().svo_pyramid_set_upload_device(self.handle, int(first), int(count), src))
 
     def build(self, first=0, count=None):
         count = self.n_frames - first if count is None else count
@@ -153,20 +275,21 @@ class PyramidSet:
 class ImagePyramid:
     """ImagePyramid(baseImage, maxPyramidLevel) — device resident (src/image_pyramid.cpp:14-52)."""
 
-    def __init__(self, base_image=None, levels=4, ctx=None):
+    def __init__(self, base_image=None, levels=4, ctx=None, camera=None):
         self.ctx = ctx or default_context()
         self.levels = int(levels)
         self.set = None
         if base_image is not None:
-            self.create_image_pyramid(base_image, levels)
+            self.create_image_pyramid(base_image, levels, camera)
 
-    def create_image_pyramid(self, base_image, levels):
+    def create_image_pyramid(self, base_image, levels, camera=None):
+        """camera: when it applies distortion, base_image is the raw image (PyramidSet.upload)."""
         img = np.ascontiguousarray(base_image, dtype=np.uint8)
         if img.ndim != 2:
             raise ValueError("ImagePyramid expects one 8-bit grey image")
         self.levels = int(levels)
         self.set = PyramidSet(1, img.shape[1], img.shape[0], self.levels, self.ctx)
-        self.set.upload(0, img[None])
+        self.set.upload(0, img[None], camera)
         self.set.build(0, 1)
 
     def get_size_image_pyramid(self):
@@ -474,7 +597,9 @@ for _m in ("append", "extend", "insert", "remove", "pop", "clear", "sort", "reve
 
 
 class Frame:
-    """Frame(camera, img, maxImagePyramid, timestamp, lastKeyframe) (src/frame.cpp:6-27)."""
+    """Frame(camera, img, maxImagePyramid, timestamp, lastKeyframe) (src/frame.cpp:6-27).  With a camera that applies
+    distortion img is the RAW image; the pyramid holds the undistorted one, and every pixel the frame's features carry
+    is an undistorted pixel."""
 
     _frame_counter = 0  # Frame::m_frameCounter
 
@@ -484,7 +609,7 @@ class Frame:
             raise RuntimeError("Image Corrupted")  # src/frame.cpp:20-24
         self.camera = camera
         self.abs_pose = np.array([0, 0, 0, 1, 0, 0, 0], dtype=np.float64)  # identity (src/frame.cpp:13)
-        self.image_pyramid = ImagePyramid(img, max_image_pyramid, ctx)
+        self.image_pyramid = ImagePyramid(img, max_image_pyramid, ctx, camera)
         self._feat_ver = [0]  # bumped by any change to the features (list or Feature attributes)
         self._soa = None      # (key, px, bearing, point, has_point) of the current features
         self.features = []
@@ -1816,12 +1941,14 @@ class Config:
     """The fields of the reference's Config (include/config.hpp) that src/system.cpp reads, with the defaults of its
     config/config.json and resource/kitti.yaml, plus what this project adds: ransac_seed (the RANSAC sampler),
     map_cell_seed (the map's cell order), max_keyframes (the literal 7 of src/system.cpp:436) and median_mode
-    (ImageAlignment's robust scale).  Visualisation and logging are not part of it."""
+    (ImageAlignment's robust scale), and d0..d4, the lens coefficients (k1, k2, p1, p2, k3) of the reference's
+    PinholeCamera, all 0 by default (KITTI's rectified images).  Visualisation and logging are not part of it."""
 
     def __init__(self, **kw):
         self.img_width, self.img_height = 1241, 376
         self.fx = self.fy = 721.5377
         self.cx, self.cy = 609.5593, 172.8540
+        self.d0 = self.d1 = self.d2 = self.d3 = self.d4 = 0.0
         self.patch_size_optical_flow = 11
         self.patch_size_image_alignment = 5
         self.min_level_image_pyramid = 0
@@ -1847,6 +1974,10 @@ class System:
     addImage -> processFirstFrame / processSecondFrame / processNewFrame / relocalisation, each step one of the
     device-backed classes above in the reference's order.
 
+    add_image takes RAW images: with any of Config.d0..d4 non-zero each is undistorted on the device ahead of its
+    pyramid (the reference's System never calls PinholeCamera::undistortImage), and everything downstream is the plain
+    pinhole model on undistorted pixels.
+
     Deliberate differences from the reference:
       * the depth estimator runs without its worker thread, i.e. the reference's own m_thread == nullptr branch
         (addFrame = updateFilters, addKeyframe = initializeFilters), so a run is a function of its images and seeds;
@@ -1866,7 +1997,7 @@ class System:
         c = self.config = config or Config()
         self.instrument = bool(instrument)  # fill timings and ba_removed (tests, tools/system_time.py); off: no cost
         self.ctx = ctx or default_context()
-        self.camera = PinholeCamera(c.img_width, c.img_height, c.fx, c.fy, c.cx, c.cy)
+        self.camera = PinholeCamera(c.img_width, c.img_height, c.fx, c.fy, c.cx, c.cy, c.d0, c.d1, c.d2, c.d3, c.d4)
         self.alignment = ImageAlignment(c.patch_size_image_alignment, c.min_level_image_pyramid,
                                         c.max_level_image_pyramid, 6, self.ctx, c.median_mode)
         self.feature_selector = FeatureSelection(c.img_width, c.img_height, c.cell_pixel_size, self.ctx)

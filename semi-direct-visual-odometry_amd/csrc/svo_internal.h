@@ -298,6 +298,26 @@ void launch_essential_mask(const EssentialArgs& a, hipStream_t s);
 // OpenCV's RANSACUpdateNumIters: the sample count that reaches `confidence` at outlier ratio `ep` (host, double)
 int essential_update_iterations(double confidence, double ep, int max_iterations);
 
+struct UndistortMapArgs {  // the fixed-point undistortion map of one camera (undistort.hip; contract: include/svo_c.h)
+    uint32_t* xy;     // [n_padded] X | Y << 16, int16 each, X clamped to [-2, width], Y to [-2, height]
+    uint16_t* frac;   // [n_padded] ay << 5 | ax
+    int64_t n, n_padded;  // width * height, and that rounded up to four (the padding's taps lie outside)
+    int32_t width, height;
+    double fx, fy, cx, cy, k1, k2, p1, p2, k3;
+};
+void launch_undistort_map(const UndistortMapArgs& a, hipStream_t s);
+
+struct UndistortArgs {  // the remap of `count` tightly packed planes through one map (undistort.hip)
+    const uint32_t* xy;
+    const uint16_t* frac;
+    const uint8_t* src;   // raw plane k at src + k * src_stride
+    uint8_t* dst;         // undistorted plane k at dst + k * dst_stride
+    int64_t src_stride, dst_stride, n;
+    int32_t width, height, count;
+    int32_t per_thread;   // images one thread walks with its map entries (grid y = count / per_thread, rounded up)
+};
+void launch_undistort_remap(const UndistortArgs& a, hipStream_t s);
+
 // FeatureSelection (feature_select.hip)
 int feature_detect_segments(int64_t npx);
 void launch_feature_detect(const uint8_t* plane, int width, int height, int thr, int* seg_counts, uint32_t* keys,

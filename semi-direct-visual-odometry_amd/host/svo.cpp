@@ -30,17 +30,56 @@ bool PinholeCamera::isInFrame(const Vec2& p, double b) const {
     return p[0] >= b && p[1] >= b && p[0] < width - b && p[1] < height - b;
 }
 
+Vec2 PinholeCamera::rawPixel(const Vec2& p) const {
+    const double x = (p[0] - cx) / fx, y = (p[1] - cy) / fy;
+    const double x2 = x * x, y2 = y * y, r2 = x2 + y2, xy2 = (2.0 * x) * y;
+    const double kr = 1.0 + ((d4 * r2 + d1) * r2 + d0) * r2;
+    const double xd = (x * kr + d2 * xy2) + d3 * (r2 + 2.0 * x2);
+    const double yd = (y * kr + d2 * (r2 + 2.0 * y2)) + d3 * xy2;
+    return {fx * xd + cx, fy * yd + cy};
+}
+Vec2 PinholeCamera::undistortedPixel(const Vec2& raw) const {
+    const double xd = (raw[0] - cx) / fx, yd = (raw[1] - cy) / fy;
+    double x = xd, y = yd;
+    for (int it = 0; it < SVO_UNDISTORT_POINT_ITERATIONS; ++it) {
+        const double x2 = x * x, y2 = y * y, r2 = x2 + y2, xy2 = (2.0 * x) * y;
+        const double kr = 1.0 + ((d4 * r2 + d1) * r2 + d0) * r2;
+        const double tx = d2 * xy2 + d3 * (r2 + 2.0 * x2), ty = d2 * (r2 + 2.0 * y2) + d3 * xy2;
+        x = (xd - tx) / kr;
+        y = (yd - ty) / kr;
+    }
+    return {fx * x + cx, fy * y + cy};
+}
+const svo_undistort_map* PinholeCamera::undistortMap(Context& ctx) const {
+    if (!m_map || m_mapCtx != ctx.get()) {
+        const svo_camera cam = c();
+        const svo_distortion d{d0, d1, d2, d3, d4};
+        svo_undistort_map* m = nullptr;
+        check(svo_undistort_map_create(ctx.get(), &cam, &d, &m));
+        m_map.reset(m, [](svo_undistort_map* q) { svo_undistort_map_destroy(q); });
+        m_mapCtx = ctx.get();
+    }
+    return m_map.get();
+}
+std::vector<uint8_t> PinholeCamera::undistortImage(Context& ctx, const uint8_t* img) const {
+    std::vector<uint8_t> out(img, img + (size_t)width * height);
+    if (applyDistortion()) check(svo_undistort_images(ctx.get(), undistortMap(ctx), img, out.data(), 1));
+    return out;
+}
+
 ImagePyramid::ImagePyramid(Context& ctx, std::size_t levels) : m_ctx(ctx), m_levels(levels) {}
 ImagePyramid::ImagePyramid(Context& ctx, const uint8_t* img, int32_t w, int32_t h, std::size_t levels)
     : m_ctx(ctx), m_levels(levels) {
     createImagePyramid(img, w, h, levels);
 }
 ImagePyramid::~ImagePyramid() { clear(); }
-void ImagePyramid::createImagePyramid(const uint8_t* img, int32_t w, int32_t h, std::size_t levels) {
+void ImagePyramid::createImagePyramid(const uint8_t* img, int32_t w, int32_t h, std::size_t levels,
+                                      const svo_undistort_map* undistort) {
     clear();
     m_levels = levels;
     check(svo_pyramid_set_create(m_ctx.get(), 1, w, h, (int32_t)levels, &m_set));
-    check(svo_pyramid_set_upload(m_set, 0, 1, img));
+    if (undistort) check(svo_pyramid_set_upload_undistort(m_set, 0, 1, img, undistort));
+    else check(svo_pyramid_set_upload(m_set, 0, 1, img));
     check(svo_pyramid_set_build(m_set, 0, 1));
     check(svo_ctx_synchronize(m_ctx.get()));
 }
@@ -75,7 +114,8 @@ Frame::Frame(Context& ctx, std::shared_ptr<PinholeCamera> camera, const uint8_t*
     static uint64_t frameCounter = 0;  // Frame::m_frameCounter
     m_id = frameCounter++;
     if (!img) throw std::runtime_error("Image Corrupted");  // src/frame.cpp:20-24
-    m_imagePyramid.createImagePyramid(img, m_camera->width, m_camera->height, maxImagePyramid);
+    m_imagePyramid.createImagePyramid(img, m_camera->width, m_camera->height, maxImagePyramid,
+                                      m_camera->applyDistortion() ? m_camera->undistortMap(ctx) : nullptr);
 }
 
 ImageAlignment::ImageAlignment(Context& ctx, uint32_t patchSize, int32_t minLevel, int32_t maxLevel, uint32_t numParameters,
@@ -814,7 +854,8 @@ void DepthEstimator::addFrame(const std::shared_ptr<Frame>& frame) {
 // ------------------------------------------------------------------ System
 System::System(Context& ctx, const Config& c)
     : m_ctx(ctx), m_config(c),
-      m_camera(std::make_shared<PinholeCamera>(PinholeCamera{c.m_imgWidth, c.m_imgHeight, c.m_fx, c.m_fy, c.m_cx, c.m_cy})),
+      m_camera(std::make_shared<PinholeCamera>(PinholeCamera{c.m_imgWidth, c.m_imgHeight, c.m_fx, c.m_fy, c.m_cx, c.m_cy,
+                                                             c.m_d0, c.m_d1, c.m_d2, c.m_d3, c.m_d4})),
       m_alignment(ctx, c.m_patchSizeImageAlignment, c.m_minLevelImagePyramid, c.m_maxLevelImagePyramid, 6, c.m_medianMode),
       m_featureSelector(ctx, c.m_imgWidth, c.m_imgHeight, c.m_cellPixelSize),
       m_map(ctx, m_camera, c.m_cellPixelSize, c.m_mapCellSeed), m_depthEstimator(ctx, &m_map),

@@ -44,13 +44,30 @@ private:
     svo_ctx* m_ctx = nullptr;
 };
 
-struct PinholeCamera {  // include/pinhole_camera.hpp:16 (undistorted)
+// include/pinhole_camera.hpp:16.  d0..d4 = (k1, k2, p1, p2, k3) in OpenCV's order describe the RAW image and are consumed
+// once per frame, ahead of the pyramid (undistortImage, Frame).  project2d, inverseProject2d, isInFrame and c() are the
+// plain pinhole and operate on UNDISTORTED pixels whatever d is: the reference's distorted project2d
+// (src/pinhole_camera.cpp:58-72) is wrong upstream, never meets an undistorted image, and is not mirrored.
+struct PinholeCamera {
     int32_t width, height;
     double fx, fy, cx, cy;
+    double d0 = 0.0, d1 = 0.0, d2 = 0.0, d3 = 0.0, d4 = 0.0;
     Vec2 project2d(const Vec3& p) const;
     Vec3 inverseProject2d(const Vec2& px) const;
     bool isInFrame(const Vec2& p, double boundary = 0.0) const;
     svo_camera c() const { return {fx, fy, cx, cy, width, height}; }
+    // any coefficient non-zero (the reference tests |d0| > 1e-5 alone: a deliberate difference, include/svo_c.h)
+    bool applyDistortion() const { return d0 != 0.0 || d1 != 0.0 || d2 != 0.0 || d3 != 0.0 || d4 != 0.0; }
+    // where the undistorted pixel p lies in the raw image (the unrounded (u, v) of the map contract), and its inverse by
+    // SVO_UNDISTORT_POINT_ITERATIONS fixed-point iterations; host only, the Python mirror's operation order
+    Vec2 rawPixel(const Vec2& p) const;
+    Vec2 undistortedPixel(const Vec2& raw) const;
+    // src/pinhole_camera.cpp:178-184 (a copy when nothing applies, :183); the device map is created on first use and
+    // kept for the context it was made on (which must outlive the camera)
+    std::vector<uint8_t> undistortImage(Context& ctx, const uint8_t* img) const;
+    const svo_undistort_map* undistortMap(Context& ctx) const;
+    mutable std::shared_ptr<svo_undistort_map> m_map;
+    mutable svo_ctx* m_mapCtx = nullptr;
 };
 
 // ImagePyramid (include/image_pyramid.hpp:23-149): device resident; copy/move deleted like the reference.
@@ -61,7 +78,9 @@ public:
     ImagePyramid(const ImagePyramid&) = delete;
     ImagePyramid& operator=(const ImagePyramid&) = delete;
     ~ImagePyramid();
-    void createImagePyramid(const uint8_t* baseImage, int32_t width, int32_t height, std::size_t maxPyramidLevel);
+    // undistort: baseImage is a raw image, remapped through this map on its way into level 0
+    void createImagePyramid(const uint8_t* baseImage, int32_t width, int32_t height, std::size_t maxPyramidLevel,
+                            const svo_undistort_map* undistort = nullptr);
     std::vector<uint8_t> getImageAtLevel(std::size_t level) const;
     std::vector<uint8_t> getGradientAtLevel(std::size_t level) const;
     std::vector<uint8_t> getBaseImage() const { return getImageAtLevel(0); }
@@ -102,7 +121,9 @@ struct Feature {  // include/feature.hpp:14
     FeatureType m_type = FeatureType::EDGE;
     Feature(Frame* frame, const Vec2& px);
 };
-struct Frame {  // include/frame.hpp:70-208 (the members the alignment path reads)
+// include/frame.hpp:70-208 (the members the alignment path reads).  With a camera that applies distortion img is the RAW
+// image; the pyramid holds the undistorted one and every feature pixel is an undistorted pixel.
+struct Frame {
     Frame(Context& ctx, std::shared_ptr<PinholeCamera> camera, const uint8_t* img, uint32_t maxImagePyramid,
           std::shared_ptr<Frame> lastKeyframe = nullptr);
     std::shared_ptr<PinholeCamera> m_camera;
@@ -341,7 +362,7 @@ void writeFeaturesInfoFile(const Frame& refFrame, const Frame& curFrame, std::os
 }  // namespace utils
 
 // Config: the fields of include/config.hpp that src/system.cpp reads (defaults: config/config.json, resource/kitti.yaml)
-// plus ransacSeed, mapCellSeed, maxKeyframes (the literal 7 of src/system.cpp:436) and medianMode.
+// plus ransacSeed, mapCellSeed, maxKeyframes (the literal 7 of src/system.cpp:436), medianMode and the lens coefficients.
 struct Config {
     int32_t m_imgWidth = 1241, m_imgHeight = 376;
     double m_fx = 721.5377, m_fy = 721.5377, m_cx = 609.5593, m_cy = 172.8540;
@@ -354,6 +375,7 @@ struct Config {
     uint64_t m_ransacSeed = 0, m_mapCellSeed = 0;
     std::size_t m_maxKeyframes = 7;
     int32_t m_medianMode = SVO_MEDIAN_REFERENCE;
+    double m_d0 = 0.0, m_d1 = 0.0, m_d2 = 0.0, m_d3 = 0.0, m_d4 = 0.0;  // the lens: k1 k2 p1 p2 k3, 0 for rectified images
 };
 
 // System (include/system.hpp, src/system.cpp:15-511): addImage -> processFirstFrame / processSecondFrame /
@@ -370,7 +392,8 @@ public:
     enum class Result : uint8_t { Success = 0, Failed = 1, Keyframe = 2 };
     struct Summary { std::size_t frames = 0, features = 0, points = 0, filters = 0, candidates = 0, keyframes = 0; };
     System(Context& ctx, const Config& config);
-    bool addImage(const uint8_t* img, uint64_t timestamp);  // :34-76
+    // :34-76.  img is the RAW image: with a lens in the Config it is undistorted on the device ahead of its pyramid
+    bool addImage(const uint8_t* img, uint64_t timestamp);
     void writeInFile(std::ostream& fileWriter) const { utils::writeInFile(m_refFrame->m_absPose, fileWriter); }
     Summary reportSummary() const;
     Status status() const { return m_systemStatus; }

@@ -43,12 +43,16 @@
 //                                  W H, cell, desired points, min points, disparity threshold, map scale, ransac
 //                                  seed, max keyframes, patch (optical flow), patch (alignment), min level, max
 //                                  level, gradient threshold, median mode, n_frames, relocalise (1: the status is set
-//                                  to relocalisation before the last frame), n_cells, the map's cell order;
+//                                  to relocalisation before the last frame), n_cells, the map's cell order, then
+//                                  optionally d0 .. d4 (the lens; the frames are then raw images);
 //                                  IMAGES.raw: the frames, W x H bytes each; prints per frame "frame k result status
 //                                  keyframe n_obs n_obs_points seeds candidates keyframes", "pose" + the cur pose[7]
 //                                  with %a, "removed" + frame:index of the features the BA removed (frame ids
 //                                  relative to the first), "time" + step=seconds, and last the trajectory lines; an
 //                                  optional PASSES argument repeats the whole run on a fresh System (timing)
+//   svo_host_check undistort_points DATA.bin   PinholeCamera::rawPixel / undistortedPixel (host only); DATA.bin (doubles):
+//                                  fx fy cx cy W H d0 .. d4 n, then n x p[2]; prints with %a per point "pt" + rawPixel(p)
+//                                  + undistortedPixel(rawPixel(p))
 #include <algorithm>
 #include <array>
 #include <chrono>
@@ -507,7 +511,11 @@ int main(int argc, char** argv) {
             const int nFrames = (int)d[19];
             const bool relocalise = d[20] != 0.0;
             const size_t nCells = (size_t)d[21];
-            if (nd != 22 + nCells) throw std::runtime_error("system: DATA.bin size mismatch");
+            if (nd != 22 + nCells && nd != 27 + nCells) throw std::runtime_error("system: DATA.bin size mismatch");
+            if (nd == 27 + nCells) {
+                const double* l = d + 22 + nCells;
+                c.m_d0 = l[0]; c.m_d1 = l[1]; c.m_d2 = l[2]; c.m_d3 = l[3]; c.m_d4 = l[4];
+            }
             std::vector<int32_t> order(nCells);
             for (size_t i = 0; i < nCells; ++i) order[i] = (int32_t)d[22 + i];
             const size_t frameBytes = (size_t)c.m_imgWidth * c.m_imgHeight;
@@ -544,7 +552,20 @@ int main(int argc, char** argv) {
             }
             return 0;
         }
-        std::fprintf(stderr, "usage: svo_host_check io | fs W H CELL THR NUM BUCKET IMAGE [EX EY]... | fv W H CELL THR IMAGE | init DATA.bin | essential DATA.bin | wba DATA.bin | system DATA.bin IMAGES.raw [PASSES]\n");
+        if (mode == "undistort_points" && argc >= 3) {
+            std::ifstream f(argv[2], std::ios::binary);
+            std::vector<char> raw((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+            const double* d = reinterpret_cast<const double*>(raw.data());
+            const size_t nd = raw.size() / sizeof(double);
+            if (nd < 12 || nd != 12 + 2 * (size_t)d[11]) throw std::runtime_error("undistort_points: DATA.bin size mismatch");
+            const PinholeCamera cam{(int32_t)d[4], (int32_t)d[5], d[0], d[1], d[2], d[3], d[6], d[7], d[8], d[9], d[10]};
+            for (size_t i = 0; i < (size_t)d[11]; ++i) {
+                const Vec2 r = cam.rawPixel({d[12 + 2 * i], d[13 + 2 * i]}), u = cam.undistortedPixel(r);
+                std::printf("pt %a %a %a %a\n", r[0], r[1], u[0], u[1]);
+            }
+            return 0;
+        }
+        std::fprintf(stderr, "usage: svo_host_check io | fs W H CELL THR NUM BUCKET IMAGE [EX EY]... | fv W H CELL THR IMAGE | init DATA.bin | essential DATA.bin | wba DATA.bin | system DATA.bin IMAGES.raw [PASSES] | undistort_points DATA.bin\n");
         return 2;
     } catch (const std::exception& e) {
         std::fprintf(stderr, "svo_host_check: %s\n", e.what());

@@ -293,8 +293,8 @@ def write_map_problem(p, directory, cell_order):
 
 def write_system_problem(config, images, cell_order, directory, relocalise=False):
     """Files for build/svo_host_check system (the C++ mirror's System): system.bin (doubles, layout in
-    host/svo_host_check.cpp: the Config fields, the number of frames, the relocalise flag, the map's cell order) and
-    images.raw (the frames).  Returns the two paths."""
+    host/svo_host_check.cpp: the Config fields, the number of frames, the relocalise flag, the map's cell order, and
+    d0..d4 when one of them is non-zero) and images.raw (the frames).  Returns the two paths."""
     import os
     c = config
     hdr = [c.fx, c.fy, c.cx, c.cy, c.img_width, c.img_height, c.cell_pixel_size,
@@ -303,6 +303,8 @@ def write_system_problem(config, images, cell_order, directory, relocalise=False
            c.patch_size_image_alignment, c.min_level_image_pyramid, c.max_level_image_pyramid,
            c.threshold_gradient_magnitude, c.median_mode, len(images), int(relocalise), len(cell_order)]
     data, raw = os.path.join(str(directory), "system.bin"), os.path.join(str(directory), "images.raw")
-    np.concatenate([np.array(hdr, np.float64), np.asarray(cell_order, np.float64)]).tofile(data)
+    d = [getattr(c, "d%d" % i, 0.0) for i in range(5)]
+    np.concatenate([np.array(hdr, np.float64), np.asarray(cell_order, np.float64),
+                    np.array(d if any(d) else [], np.float64)]).tofile(data)
     np.ascontiguousarray(images, np.uint8).tofile(raw)
     return data, raw

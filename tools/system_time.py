@@ -13,7 +13,10 @@ The Python mirror (svo_amd.System) and the C++ mirror (svo_amd::System through b
 process, its first pass untimed as well) are timed on the same frames with the same cell order and printed side by side:
 every key once per mirror ("python", "cpp").
 
-    python tools/system_time.py [--frames 32] [--reps 3]
+With --lens k1,k2,p1,p2,k3 the camera has that lens: the frames are made raw on the host first (tests/undistort_ref.py
+distort_image) and the System undistorts them on the device, so "frame" then includes the remap.
+
+    python tools/system_time.py [--frames 32] [--reps 3] [--lens k1,k2,p1,p2,k3]
 """
 import argparse
 import json
@@ -90,9 +93,18 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=32)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--lens", default="")
     a = ap.parse_args()
     images, _ = SC.make_sequence(a.frames, W, H)
     cfg = svo_amd.Config(desired_detected_points_for_initialization=1000)  # SSC keeps about half: ~500 of 546 cells
+    lens = [float(v) for v in a.lens.split(",")] if a.lens else []
+    if lens:
+        import numpy as np
+        import undistort_ref as U
+        cam = dict(fx=cfg.fx, fy=cfg.fy, cx=cfg.cx, cy=cfg.cy, width=W, height=H)
+        images = np.stack([U.distort_image(img, cam, lens) for img in images])
+        for k, v in enumerate(lens):
+            setattr(cfg, "d%d" % k, v)
     one_pass(images, cfg)  # warm-up
     rows = []
     for _ in range(a.reps):
@@ -100,7 +112,7 @@ def main():
         rows += r[2:]  # the frames processNewFrame handled
     S = svo_amd.System
     cpp = [r for p in cpp_passes(images, cfg, system.map.cell_orders, a.reps + 1)[1:] for r in p[2:]]
-    out = {"tool": "system_time", "width": W, "height": H, "frames": a.frames, "reps": a.reps,
+    out = {"tool": "system_time", "width": W, "height": H, "frames": a.frames, "reps": a.reps, "lens": lens,
            "keyframes_in_map": system.map.size_keyframes(), "seeds": system.depth_estimator.number_filters(),
            "python": summarise(rows, S), "cpp": summarise(cpp, S)}
     print(json.dumps(out))

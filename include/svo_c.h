@@ -640,6 +640,54 @@ int svo_pyramid_set_upload_undistort(svo_pyramid_set* set, int32_t first, int32_
 int svo_pyramid_set_upload_undistort_device(svo_pyramid_set* set, int32_t first, int32_t count,
                                             const uint8_t* dev_images, const svo_undistort_map* map);
 
+/* ---------------------------------------------------------------- pixel formats: colour and 16-bit frames to grey
+ * Replaces the cv::imread(.., IMREAD_GRAYSCALE) the reference reads every frame with (src/main.cpp:105): the step from
+ * what a camera, a decoder or a file holds to the 8-bit grey plane that is level 0 of a pyramid.  It runs on the device
+ * on the frame's way into the set, ahead of the undistortion (convert first, then remap).  The arithmetic below is THIS
+ * PROJECT'S CONTRACT, in integers:
+ *   colour (BGR8, RGB8, BGRA8, RGBA8; one byte per channel in the named order; alpha is ignored):
+ *       Y = (4899*R + 9617*G + 1868*B + 8192) >> 14
+ *     The weights sum to 16384, so R = G = B = v gives v and nothing saturates.  This is the rule OpenCV documents for
+ *     its 8-bit COLOR_BGR2GRAY / COLOR_RGB2GRAY and the rule tests/golden/make_golden_refimages.py built refimages.npz
+ *     with.  OpenCV is not part of the reference tree or of this project's build, so there is NO recorded OpenCV result
+ *     that anchors it; and it is not claimed to equal imread(IMREAD_GRAYSCALE), which converts inside libpng / libjpeg.
+ *   GRAY16 (native-endian uint16):
+ *       Y = min(255, v >> shift)        shift in 0..8
+ *     shift = 8 keeps the high byte, which is what an 8-bit imread keeps of a 16-bit PNG; shift = 4 serves 12-bit
+ *     sensors.
+ *   GRAY8: a copy that honours the strides (a decoder's pitched luma plane).
+ * Layout: `count` images of width x height pixels; row y of image k starts at byte k*image_stride + y*row_stride.  A
+ * stride of 0 means packed: row_stride = width*bytes_per_pixel, image_stride = row_stride*height.  The bytes a call
+ * reads are exactly [0, image_stride*(count-1) + row_stride*(height-1) + width*bytes_per_pixel): no byte before the
+ * pointer and none past that end is touched, whatever the pointer's alignment.  A GRAY16 pointer and GRAY16 strides are
+ * even; nothing else is required of the pointer's or the strides' alignment. */
+enum { SVO_PIXEL_GRAY8 = 0, SVO_PIXEL_BGR8, SVO_PIXEL_RGB8, SVO_PIXEL_BGRA8, SVO_PIXEL_RGBA8, SVO_PIXEL_GRAY16 };
+typedef struct {
+    int32_t format;        /* SVO_PIXEL_* */
+    int32_t shift;         /* GRAY16 only: 0..8; ignored otherwise */
+    int64_t row_stride;    /* bytes between rows;   0 = width * bytes_per_pixel */
+    int64_t image_stride;  /* bytes between images; 0 = row_stride * height */
+} svo_image_layout;
+/* Host only: the number of bytes a call with this layout reads (0 for count = 0).  SVO_ERR_ARG with a text for an
+ * unknown format, a GRAY16 shift outside 0..8, a row stride below width*bytes_per_pixel, an image stride below
+ * row_stride*(height-1) + width*bytes_per_pixel, an odd GRAY16 stride, width or height < 1, count < 0.  Every entry
+ * point below validates its layout through this function. */
+int svo_image_layout_bytes(const svo_image_layout* layout, int32_t width, int32_t height, int32_t count,
+                           int64_t* bytes);
+/* `count` images to grey, host to host (count*width*height bytes out, packed).  Synchronous; the counterpart of
+ * svo_undistort_images. */
+int svo_convert_images(svo_ctx* ctx, const svo_image_layout* layout, int32_t width, int32_t height, int32_t count,
+                       const void* host_in, uint8_t* host_out);
+/* svo_pyramid_set_upload / _upload_device of images in `layout` (width and height are the set's): they are converted
+ * into level 0 of frames [first, first+count).  `map` may be NULL; with a map the result is, bit for bit, the grey
+ * image of the contract above remapped by the undistortion contract.  Stream order and waits are those of the plain
+ * uploads; the host form stages the raw bytes in the context's per-call device block first.  SVO_ERR_ARG for a NULL
+ * layout, an odd GRAY16 pointer, a map of another size or of another context. */
+int svo_pyramid_set_upload_format(svo_pyramid_set* set, int32_t first, int32_t count, const void* host_images,
+                                  const svo_image_layout* layout, const svo_undistort_map* map);
+int svo_pyramid_set_upload_format_device(svo_pyramid_set* set, int32_t first, int32_t count, const void* dev_images,
+                                         const svo_image_layout* layout, const svo_undistort_map* map);
+
 #ifdef __cplusplus
 }
 #endif

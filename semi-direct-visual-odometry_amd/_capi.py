@@ -29,6 +29,17 @@ class SvoDistortion(ctypes.Structure):
     _fields_ = [("k1", c_double), ("k2", c_double), ("p1", c_double), ("p2", c_double), ("k3", c_double)]
 
 
+class SvoImageLayout(ctypes.Structure):
+    _fields_ = [("format", c_int32), ("shift", c_int32), ("row_stride", ctypes.c_int64),
+                ("image_stride", ctypes.c_int64)]
+
+
+# SVO_PIXEL_* by the names the mirrors use, and (bytes per pixel, numpy dtype, channels) of each
+PIXEL_FORMATS = {"gray8": 0, "bgr8": 1, "rgb8": 2, "bgra8": 3, "rgba8": 4, "gray16": 5}
+PIXEL_SHAPES = {"gray8": (1, "uint8", 0), "bgr8": (3, "uint8", 3), "rgb8": (3, "uint8", 3), "bgra8": (4, "uint8", 4),
+                "rgba8": (4, "uint8", 4), "gray16": (2, "uint16", 0)}
+
+
 class SvoAlignParams(ctypes.Structure):
     _fields_ = [("patch_size", c_int32), ("min_level", c_int32), ("max_level", c_int32), ("median_mode", c_int32)]
 
@@ -127,6 +138,10 @@ _SIGNATURES = [
     ("svo_undistort_images", c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32]),
     ("svo_pyramid_set_upload_undistort", c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     ("svo_pyramid_set_upload_undistort_device", c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    ("svo_image_layout_bytes", c_int32, [c_void_p, c_int32, c_int32, c_int32, ctypes.POINTER(ctypes.c_int64)]),
+    ("svo_convert_images", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    ("svo_pyramid_set_upload_format", c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    ("svo_pyramid_set_upload_format_device", c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
 ]
 
 EXPORTED = [s[0] for s in _SIGNATURES]

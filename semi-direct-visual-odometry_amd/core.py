@@ -201,6 +201,55 @@ class PinholeCamera:
         return p[0] >= boundary and p[1] >= boundary and p[0] < self.width - boundary and p[1] < self.height - boundary
 
 
+def _pixel_format(pixel_format):
+    if pixel_format not in _capi.PIXEL_FORMATS:
+        raise ValueError(f"unknown pixel format {pixel_format!r}: one of {', '.join(_capi.PIXEL_FORMATS)}")
+    return _capi.PIXEL_FORMATS[pixel_format]
+
+
+def _image_layout(images, pixel_format, gray16_shift, height, width):
+    """(array, count, svo_image_layout) of one image or a stack in a pixel format (include/svo_c.h, "pixel formats").
+    The format is never guessed: shape and dtype must fit it (ValueError).  A view whose pixels are contiguous and
+    whose rows and images lie at non-negative strides that clear a row / an image is passed with its strides; anything
+    else is made contiguous first."""
+    fmt = _pixel_format(pixel_format)
+    bpp, dtype, channels = _capi.PIXEL_SHAPES[pixel_format]
+    a = np.asarray(images)
+    if a.dtype != np.dtype(dtype):
+        raise ValueError(f"pixel format {pixel_format!r} takes {dtype} images, not {a.dtype}")
+    want = (height, width, channels) if channels else (height, width)
+    if a.ndim not in (len(want), len(want) + 1) or a.shape[a.ndim - len(want):] != want:
+        raise ValueError(f"image shape {a.shape} does not fit pixel format {pixel_format!r}: "
+                         f"{want} or (count,) + {want}")
+    stacked = a.ndim == len(want) + 1
+    count = a.shape[0] if stacked else 1
+    item = a.dtype.itemsize
+    row_bytes = width * bpp
+    row = a.strides[-len(want)] if height > 1 else row_bytes
+    image = a.strides[0] if stacked and count > 1 else row * height
+    pixels_ok = a.flags.aligned and a.strides[-1] == item and (not channels or a.strides[-2] == bpp)
+    if not (pixels_ok and row >= row_bytes and image >= row * (height - 1) + row_bytes):
+        a = np.require(a, requirements=["C", "A"])  # contiguous and aligned
+        row, image = row_bytes, row_bytes * height
+    return a, count, _capi.SvoImageLayout(fmt, int(gray16_shift), row, image)
+
+
+def convert_images(images, pixel_format, gray16_shift=8, ctx=None):
+    """The grey image(s) of one (h, w[, channels]) image or a stack in a pixel format, on the device, host to host
+    (svo_convert_images)."""
+    a = np.asarray(images)
+    channels = _capi.PIXEL_SHAPES[pixel_format][2] if pixel_format in _capi.PIXEL_FORMATS else 0
+    base = 3 if channels else 2
+    if a.ndim not in (base, base + 1):
+        raise ValueError(f"image shape {a.shape} does not fit pixel format {pixel_format!r}")
+    height, width = a.shape[a.ndim - base], a.shape[a.ndim - base + 1]
+    a, count, layout = _image_layout(a, pixel_format, gray16_shift, height, width)
+    out = np.empty(((count,) if a.ndim == base + 1 else ()) + (height, width), np.uint8)
+    ctx = ctx or default_context()
+    check(lib().svo_convert_images(ctx.handle, ctypes.byref(layout), width, height, count, ptr(a), ptr(out)))
+    return out
+
+
 class PyramidSet:
     """n_frames device-resident (image, gradient) stacks of equal geometry (svo_pyramid_set)."""
 
@@ -212,9 +261,20 @@ class PyramidSet:
                                            ctypes.byref(h)))
         self.handle = h
 
-    def upload(self, first, images, camera=None):
+    def _map_handle(self, camera):
+        return camera.undistort_map(self.ctx).handle if camera is not None and camera.apply_distortion else None
+
+    def upload(self, first, images, camera=None, pixel_format="gray8", gray16_shift=8):
         """Level 0 of frames [first, first + count).  With a camera that applies distortion the images are RAW: they
-        are undistorted on the device on their way in (svo_pyramid_set_upload_undistort)."""
+        are undistorted on the device on their way in (svo_pyramid_set_upload_undistort).  pixel_format other than
+        "gray8": (h, w, 3 or 4) uint8 colour or (h, w) uint16 images, or stacks of them, converted to grey on the
+        device ahead of that (svo_pyramid_set_upload_format; gray16_shift: Y = min(255, v >> shift))."""
+        if _pixel_format(pixel_format) != 0:
+            imgs, count, layout = _image_layout(images, pixel_format, gray16_shift, self.height, self.width)
+            check(lib().svo_pyramid_set_upload_format(self.handle, int(first), count, ptr(imgs), ctypes.byref(layout),
+                                                      self._map_handle(camera)))
+            self.ctx.synchronize()  # the host buffer may die after return
+            return
         imgs = np.ascontiguousarray(images, dtype=np.uint8)
         count = imgs.shape[0] if imgs.ndim == 3 else 1
         if imgs.shape[-2:] != (self.height, self.width):
@@ -226,11 +286,19 @@ class PyramidSet:
             check(lib().svo_pyramid_set_upload(self.handle, int(first), count, ptr(imgs)))
         self.ctx.synchronize()  # the host buffer may die after return
 
-    def upload_device(self, first, count, dev_ptr, camera=None):
+    def upload_device(self, first, count, dev_ptr, camera=None, pixel_format="gray8", gray16_shift=8, row_stride=0,
+                      image_stride=0):
         """upload() from device memory (count tightly packed images at the address dev_ptr), stream-ordered: the
         memory must stay untouched until the context stream has passed the copy (svo_pyramid_set_upload_device, or
-        svo_pyramid_set_upload_undistort_device with a camera that applies distortion)."""
+        svo_pyramid_set_upload_undistort_device with a camera that applies distortion).  With a pixel_format other
+        than "gray8", or strides in bytes (0: packed), svo_pyramid_set_upload_format_device."""
         src = ctypes.c_void_p(int(dev_ptr))
+        fmt = _pixel_format(pixel_format)
+        if fmt != 0 or row_stride or image_stride:
+            layout = _capi.SvoImageLayout(fmt, int(gray16_shift), int(row_stride), int(image_stride))
+            check(lib().svo_pyramid_set_upload_format_device(self.handle, int(first), int(count), src,
+                                                             ctypes.byref(layout), self._map_handle(camera)))
+            return
         if camera is not None and camera.apply_distortion:
             check(lib().svo_pyramid_set_upload_undistort_device(self.handle, int(first), int(count), src,
                                                                 camera.undistort_map(self.ctx).handle))
@@ -275,15 +343,26 @@ class PyramidSet:
 class ImagePyramid:
     """ImagePyramid(baseImage, maxPyramidLevel) — device resident (src/image_pyramid.cpp:14-52)."""
 
-    def __init__(self, base_image=None, levels=4, ctx=None, camera=None):
+    def __init__(self, base_image=None, levels=4, ctx=None, camera=None, pixel_format="gray8", gray16_shift=8):
         self.ctx = ctx or default_context()
         self.levels = int(levels)
         self.set = None
         if base_image is not None:
-            self.create_image_pyramid(base_image, levels, camera)
+            self.create_image_pyramid(base_image, levels, camera, pixel_format, gray16_shift)
 
-    def create_image_pyramid(self, base_image, levels, camera=None):
-        """camera: when it applies distortion, base_image is the raw image (PyramidSet.upload)."""
+    def create_image_pyramid(self, base_image, levels, camera=None, pixel_format="gray8", gray16_shift=8):
+        """camera: when it applies distortion, base_image is the raw image (PyramidSet.upload).  pixel_format: what
+        base_image holds, (h, w) grey or (h, w, channels) colour; level 0 is its grey image (PyramidSet.upload)."""
+        if _pixel_format(pixel_format) != 0:
+            img = np.asarray(base_image)
+            if img.ndim != (3 if _capi.PIXEL_SHAPES[pixel_format][2] else 2):
+                raise ValueError(f"ImagePyramid expects one {pixel_format} image, not an array of shape {img.shape}")
+            _image_layout(img, pixel_format, gray16_shift, img.shape[0], img.shape[1])  # (before anything is allocated)
+            self.levels = int(levels)
+            self.set = PyramidSet(1, img.shape[1], img.shape[0], self.levels, self.ctx)
+            self.set.upload(0, img, camera, pixel_format, gray16_shift)
+            self.set.build(0, 1)
+            return
         img = np.ascontiguousarray(base_image, dtype=np.uint8)
         if img.ndim != 2:
             raise ValueError("ImagePyramid expects one 8-bit grey image")
@@ -603,13 +682,18 @@ class Frame:
 
     _frame_counter = 0  # Frame::m_frameCounter
 
-    def __init__(self, camera, image, max_image_pyramid, timestamp=0, last_keyframe=None, ctx=None):
+    def __init__(self, camera, image, max_image_pyramid, timestamp=0, last_keyframe=None, ctx=None,
+                 pixel_format="gray8", gray16_shift=8):
         img = np.asarray(image)
-        if img.dtype != np.uint8 or img.ndim != 2 or img.shape != (camera.height, camera.width):
+        if _pixel_format(pixel_format) != 0:  # colour or 16-bit: the pyramid's level 0 is the frame's grey image
+            if img.ndim != (3 if _capi.PIXEL_SHAPES[pixel_format][2] else 2):
+                raise ValueError(f"Frame expects one {pixel_format} image, not an array of shape {img.shape}")
+            _image_layout(img, pixel_format, gray16_shift, camera.height, camera.width)
+        elif img.dtype != np.uint8 or img.ndim != 2 or img.shape != (camera.height, camera.width):
             raise RuntimeError("Image Corrupted")  # src/frame.cpp:20-24
         self.camera = camera
         self.abs_pose = np.array([0, 0, 0, 1, 0, 0, 0], dtype=np.float64)  # identity (src/frame.cpp:13)
-        self.image_pyramid = ImagePyramid(img, max_image_pyramid, ctx, camera)
+        self.image_pyramid = ImagePyramid(img, max_image_pyramid, ctx, camera, pixel_format, gray16_shift)
         self._feat_ver = [0]  # bumped by any change to the features (list or Feature attributes)
         self._soa = None      # (key, px, bearing, point, has_point) of the current features
         self.features = []
@@ -1942,13 +2026,16 @@ class Config:
     config/config.json and resource/kitti.yaml, plus what this project adds: ransac_seed (the RANSAC sampler),
     map_cell_seed (the map's cell order), max_keyframes (the literal 7 of src/system.cpp:436) and median_mode
     (ImageAlignment's robust scale), and d0..d4, the lens coefficients (k1, k2, p1, p2, k3) of the reference's
-    PinholeCamera, all 0 by default (KITTI's rectified images).  Visualisation and logging are not part of it."""
+    PinholeCamera, all 0 by default (KITTI's rectified images), and pixel_format / gray16_shift, what add_image is handed
+    ("gray8" by default; include/svo_c.h, "pixel formats").  Visualisation and logging are not part of it."""
 
     def __init__(self, **kw):
         self.img_width, self.img_height = 1241, 376
         self.fx = self.fy = 721.5377
         self.cx, self.cy = 609.5593, 172.8540
         self.d0 = self.d1 = self.d2 = self.d3 = self.d4 = 0.0
+        self.pixel_format = "gray8"  # what add_image is handed: gray8, bgr8, rgb8, bgra8, rgba8 or gray16
+        self.gray16_shift = 8        # gray16: Y = min(255, v >> shift)
         self.patch_size_optical_flow = 11
         self.patch_size_image_alignment = 5
         self.min_level_image_pyramid = 0
@@ -1974,9 +2061,9 @@ class System:
     addImage -> processFirstFrame / processSecondFrame / processNewFrame / relocalisation, each step one of the
     device-backed classes above in the reference's order.
 
-    add_image takes RAW images: with any of Config.d0..d4 non-zero each is undistorted on the device ahead of its
-    pyramid (the reference's System never calls PinholeCamera::undistortImage), and everything downstream is the plain
-    pinhole model on undistorted pixels.
+    add_image takes RAW images in Config.pixel_format (colour and 16-bit frames become grey on the device first); with
+    any of Config.d0..d4 non-zero each is undistorted on the device ahead of its pyramid (the reference's System never
+    calls PinholeCamera::undistortImage), and everything downstream is the plain pinhole model on undistorted pixels.
 
     Deliberate differences from the reference:
       * the depth estimator runs without its worker thread, i.e. the reference's own m_thread == nullptr branch
@@ -2031,7 +2118,7 @@ class System:
             self.timings, self.ba_removed = {}, []
         c = self.config
         self.cur_frame = self._timed("frame", Frame, self.camera, img, c.max_level_image_pyramid + 1, timestamp,
-                                     self.active_keyframe, self.ctx)
+                                     self.active_keyframe, self.ctx, c.pixel_format, c.gray16_shift)
         res = System.FAILED
         if self.status == System.PROCESS_NEW_FRAME:
             res = self.process_new_frame()

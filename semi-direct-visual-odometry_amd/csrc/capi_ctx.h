@@ -120,6 +120,13 @@ inline int check_set(const svo_ctx* c, const svo_pyramid_set* p, const svo_camer
     return SVO_OK;
 }
 
+// The undistortion map as an argument of another stage's upload (capi_undistort.hip owns the object): not null, of
+// the set's context and size; and the remap of `count` packed device planes at `dev_src` into level 0 of frames
+// [first, first + count), queued on s.
+int check_map_for_set(const svo_pyramid_set* p, const svo_undistort_map* m, const char* entry);
+void launch_remap_into_set(const svo_undistort_map* m, const uint8_t* dev_src, svo_pyramid_set* p, int32_t first,
+                           int32_t count, hipStream_t s);
+
 // the pinhole intrinsics of a kernel argument block
 template <class A>
 void fill_camera(A& a, const svo_camera* cam) { a.fx = cam->fx; a.fy = cam->fy; a.cx = cam->cx; a.cy = cam->cy; }

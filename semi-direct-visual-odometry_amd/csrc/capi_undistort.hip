@@ -45,29 +45,42 @@ int check_map(const svo_ctx* c, const svo_undistort_map* m, const char* entry) {
 int upload_undistort(svo_pyramid_set* p, int32_t first, int32_t count, const uint8_t* images, bool on_device,
                      const svo_undistort_map* m, const char* entry) {
     if (!p || !images) return fail(SVO_ERR_ARG, "%s: null argument", entry);
-    if (int r = check_map(p->ctx, m, entry)) return r;
-    if (m->width != p->width || m->height != p->height)
-        return fail(SVO_ERR_ARG, "%s: the undistort map is %dx%d, the pyramid set %dx%d", entry, m->width, m->height,
-                    p->width, p->height);
+    if (int r = check_map_for_set(p, m, entry)) return r;
     if (first < 0 || count < 0 || first + count > p->n_frames) return fail(SVO_ERR_ARG, "%s: frames out of range", entry);
     if (count == 0) return SVO_OK;
     svo_ctx* c = p->ctx;
     SVO_HIP(hipSetDevice(c->device));
     SVO_HIP(set_join(p));
     hipStream_t s = ctx_stream(c);
-    svo::UndistortArgs a = remap_args(m, count);
-    a.src_stride = m->n;
-    a.dst = p->d_base + (size_t)first * p->stride;  // level 0 of the intensity stack
-    a.dst_stride = p->stride;
+    const uint8_t* src = images;
     Block blk(c, s);
-    if (on_device) a.src = images;
-    else blk.in(&a.src, images, (size_t)count * (size_t)m->n);  // the raw images' staging: the context's per-call block
+    if (!on_device) blk.in(&src, images, (size_t)count * (size_t)m->n);  // the raw images' staging: the context's per-call block
     if (!on_device && blk.alloc() == hipSuccess) blk.upload();
-    blk.launch([&] { svo::launch_undistort_remap(a, s); });
+    blk.launch([&] { launch_remap_into_set(m, src, p, first, count, s); });
     if (!blk.ok()) return fail(SVO_ERR_HIP, "%s: %s", entry, hipGetErrorString(blk.err));
     return SVO_OK;
 }
 }  // namespace
+
+namespace svo::shim {
+int check_map_for_set(const svo_pyramid_set* p, const svo_undistort_map* m, const char* entry) {
+    if (int r = check_map(p->ctx, m, entry)) return r;
+    if (m->width != p->width || m->height != p->height)
+        return fail(SVO_ERR_ARG, "%s: the undistort map is %dx%d, the pyramid set %dx%d", entry, m->width, m->height,
+                    p->width, p->height);
+    return SVO_OK;
+}
+
+void launch_remap_into_set(const svo_undistort_map* m, const uint8_t* dev_src, svo_pyramid_set* p, int32_t first,
+                           int32_t count, hipStream_t s) {
+    svo::UndistortArgs a = remap_args(m, count);
+    a.src = dev_src;
+    a.src_stride = m->n;
+    a.dst = p->d_base + (size_t)first * p->stride;  // level 0 of the intensity stack
+    a.dst_stride = p->stride;
+    svo::launch_undistort_remap(a, s);
+}
+}  // namespace svo::shim
 
 extern "C" {
 int svo_undistort_map_create(svo_ctx* c, const svo_camera* cam, const svo_distortion* d, svo_undistort_map** out) {

@@ -318,6 +318,9 @@ struct UndistortArgs {  // the remap of `count` tightly packed planes through on
 };
 void launch_undistort_remap(const UndistortArgs& a, hipStream_t s);
 
+struct ConvertArgs;  // convert_math.h: `count` images of a pixel format to packed grey planes (convert.hip)
+void launch_convert(const ConvertArgs& a, int32_t format, hipStream_t s);
+
 // FeatureSelection (feature_select.hip)
 int feature_detect_segments(int64_t npx);
 void launch_feature_detect(const uint8_t* plane, int width, int height, int thr, int* seg_counts, uint32_t* keys,

@@ -72,6 +72,10 @@ ImagePyramid::ImagePyramid(Context& ctx, const uint8_t* img, int32_t w, int32_t 
     : m_ctx(ctx), m_levels(levels) {
     createImagePyramid(img, w, h, levels);
 }
+ImagePyramid::ImagePyramid(Context& ctx, const ImageView& img, int32_t w, int32_t h, std::size_t levels)
+    : m_ctx(ctx), m_levels(levels) {
+    createImagePyramid(img, w, h, levels);
+}
 ImagePyramid::~ImagePyramid() { clear(); }
 void ImagePyramid::createImagePyramid(const uint8_t* img, int32_t w, int32_t h, std::size_t levels,
                                       const svo_undistort_map* undistort) {
@@ -80,6 +84,15 @@ void ImagePyramid::createImagePyramid(const uint8_t* img, int32_t w, int32_t h, 
     check(svo_pyramid_set_create(m_ctx.get(), 1, w, h, (int32_t)levels, &m_set));
     if (undistort) check(svo_pyramid_set_upload_undistort(m_set, 0, 1, img, undistort));
     else check(svo_pyramid_set_upload(m_set, 0, 1, img));
+    check(svo_pyramid_set_build(m_set, 0, 1));
+    check(svo_ctx_synchronize(m_ctx.get()));
+}
+void ImagePyramid::createImagePyramid(const ImageView& img, int32_t w, int32_t h, std::size_t levels,
+                                      const svo_undistort_map* undistort) {
+    clear();
+    m_levels = levels;
+    check(svo_pyramid_set_create(m_ctx.get(), 1, w, h, (int32_t)levels, &m_set));
+    check(svo_pyramid_set_upload_format(m_set, 0, 1, img.data, &img.layout, undistort));
     check(svo_pyramid_set_build(m_set, 0, 1));
     check(svo_ctx_synchronize(m_ctx.get()));
 }
@@ -108,12 +121,24 @@ void ImagePyramid::clear() {
 Feature::Feature(Frame* frame, const Vec2& px)
     : m_frame(frame), m_pixelPosition(px), m_bearingVec(frame->m_camera->inverseProject2d(px)) {}
 
+static uint64_t nextFrameId() {
+    static uint64_t frameCounter = 0;  // Frame::m_frameCounter
+    return frameCounter++;
+}
+
 Frame::Frame(Context& ctx, std::shared_ptr<PinholeCamera> camera, const uint8_t* img, uint32_t maxImagePyramid,
              std::shared_ptr<Frame> lastKeyframe)
     : m_camera(std::move(camera)), m_imagePyramid(ctx, maxImagePyramid), m_lastKeyframe(std::move(lastKeyframe)) {
-    static uint64_t frameCounter = 0;  // Frame::m_frameCounter
-    m_id = frameCounter++;
+    m_id = nextFrameId();
     if (!img) throw std::runtime_error("Image Corrupted");  // src/frame.cpp:20-24
+    m_imagePyramid.createImagePyramid(img, m_camera->width, m_camera->height, maxImagePyramid,
+                                      m_camera->applyDistortion() ? m_camera->undistortMap(ctx) : nullptr);
+}
+Frame::Frame(Context& ctx, std::shared_ptr<PinholeCamera> camera, const ImageView& img, uint32_t maxImagePyramid,
+             std::shared_ptr<Frame> lastKeyframe)
+    : m_camera(std::move(camera)), m_imagePyramid(ctx, maxImagePyramid), m_lastKeyframe(std::move(lastKeyframe)) {
+    m_id = nextFrameId();
+    if (!img.data) throw std::runtime_error("Image Corrupted");  // src/frame.cpp:20-24
     m_imagePyramid.createImagePyramid(img, m_camera->width, m_camera->height, maxImagePyramid,
                                       m_camera->applyDistortion() ? m_camera->undistortMap(ctx) : nullptr);
 }
@@ -886,6 +911,13 @@ template <class F> void System::runBA(const std::vector<std::shared_ptr<Frame>>&
 }
 
 bool System::addImage(const uint8_t* img, uint64_t timestamp) {
+    if (m_config.m_pixelFormat == SVO_PIXEL_GRAY8) return addFrame(img, timestamp);
+    return addFrame(ImageView{img, svo_image_layout{m_config.m_pixelFormat, m_config.m_gray16Shift, 0, 0}}, timestamp);
+}
+
+bool System::addImage(const ImageView& img, uint64_t timestamp) { return addFrame(img, timestamp); }
+
+template <class Image> bool System::addFrame(const Image& img, uint64_t timestamp) {
     if (m_instrument) {
         m_timings.clear();
         m_baRemoved.clear();

@@ -70,16 +70,27 @@ struct PinholeCamera {
     mutable svo_ctx* m_mapCtx = nullptr;
 };
 
+// An image in one of the pixel formats of include/svo_c.h ("pixel formats"): colour, 16-bit or pitched 8-bit grey.
+// Wherever one is taken, level 0 of the pyramid is its grey image by that contract (converted on the device, ahead
+// of the undistortion).  The format is never guessed.
+struct ImageView {
+    const void* data;
+    svo_image_layout layout;  // format, GRAY16 shift, row and image strides in bytes (0: packed)
+};
+
 // ImagePyramid (include/image_pyramid.hpp:23-149): device resident; copy/move deleted like the reference.
 class ImagePyramid {
 public:
     ImagePyramid(Context& ctx, std::size_t maxPyramidLevel);
     ImagePyramid(Context& ctx, const uint8_t* baseImage, int32_t width, int32_t height, std::size_t maxPyramidLevel);
+    ImagePyramid(Context& ctx, const ImageView& baseImage, int32_t width, int32_t height, std::size_t maxPyramidLevel);
     ImagePyramid(const ImagePyramid&) = delete;
     ImagePyramid& operator=(const ImagePyramid&) = delete;
     ~ImagePyramid();
     // undistort: baseImage is a raw image, remapped through this map on its way into level 0
     void createImagePyramid(const uint8_t* baseImage, int32_t width, int32_t height, std::size_t maxPyramidLevel,
+                            const svo_undistort_map* undistort = nullptr);
+    void createImagePyramid(const ImageView& baseImage, int32_t width, int32_t height, std::size_t maxPyramidLevel,
                             const svo_undistort_map* undistort = nullptr);
     std::vector<uint8_t> getImageAtLevel(std::size_t level) const;
     std::vector<uint8_t> getGradientAtLevel(std::size_t level) const;
@@ -125,6 +136,8 @@ struct Feature {  // include/feature.hpp:14
 // image; the pyramid holds the undistorted one and every feature pixel is an undistorted pixel.
 struct Frame {
     Frame(Context& ctx, std::shared_ptr<PinholeCamera> camera, const uint8_t* img, uint32_t maxImagePyramid,
+          std::shared_ptr<Frame> lastKeyframe = nullptr);
+    Frame(Context& ctx, std::shared_ptr<PinholeCamera> camera, const ImageView& img, uint32_t maxImagePyramid,
           std::shared_ptr<Frame> lastKeyframe = nullptr);
     std::shared_ptr<PinholeCamera> m_camera;
     Pose m_absPose{0, 0, 0, 1, 0, 0, 0};
@@ -362,7 +375,8 @@ void writeFeaturesInfoFile(const Frame& refFrame, const Frame& curFrame, std::os
 }  // namespace utils
 
 // Config: the fields of include/config.hpp that src/system.cpp reads (defaults: config/config.json, resource/kitti.yaml)
-// plus ransacSeed, mapCellSeed, maxKeyframes (the literal 7 of src/system.cpp:436), medianMode and the lens coefficients.
+// plus ransacSeed, mapCellSeed, maxKeyframes (the literal 7 of src/system.cpp:436), medianMode, the lens coefficients and
+// the pixel format of the frames.
 struct Config {
     int32_t m_imgWidth = 1241, m_imgHeight = 376;
     double m_fx = 721.5377, m_fy = 721.5377, m_cx = 609.5593, m_cy = 172.8540;
@@ -376,6 +390,8 @@ struct Config {
     std::size_t m_maxKeyframes = 7;
     int32_t m_medianMode = SVO_MEDIAN_REFERENCE;
     double m_d0 = 0.0, m_d1 = 0.0, m_d2 = 0.0, m_d3 = 0.0, m_d4 = 0.0;  // the lens: k1 k2 p1 p2 k3, 0 for rectified images
+    // what addImage(const uint8_t*, ..) is handed, packed: SVO_PIXEL_*; and the GRAY16 shift, Y = min(255, v >> shift)
+    int32_t m_pixelFormat = SVO_PIXEL_GRAY8, m_gray16Shift = 8;
 };
 
 // System (include/system.hpp, src/system.cpp:15-511): addImage -> processFirstFrame / processSecondFrame /
@@ -393,7 +409,9 @@ public:
     struct Summary { std::size_t frames = 0, features = 0, points = 0, filters = 0, candidates = 0, keyframes = 0; };
     System(Context& ctx, const Config& config);
     // :34-76.  img is the RAW image: with a lens in the Config it is undistorted on the device ahead of its pyramid
+    // (packed, in the Config's pixel format)
     bool addImage(const uint8_t* img, uint64_t timestamp);
+    bool addImage(const ImageView& img, uint64_t timestamp);  // the view's own format and strides
     void writeInFile(std::ostream& fileWriter) const { utils::writeInFile(m_refFrame->m_absPose, fileWriter); }
     Summary reportSummary() const;
     Status status() const { return m_systemStatus; }
@@ -410,6 +428,7 @@ public:
     const std::vector<std::pair<uint64_t, std::size_t>>& baRemoved() const { return m_baRemoved; }
 
 private:
+    template <class Image> bool addFrame(const Image& img, uint64_t timestamp);  // :34-76 for either kind of image
     Result processFirstFrame();   // :78-115
     Result processSecondFrame();  // :117-302
     Result processNewFrame();     // :304-446

@@ -44,8 +44,9 @@
 //                                  seed, max keyframes, patch (optical flow), patch (alignment), min level, max
 //                                  level, gradient threshold, median mode, n_frames, relocalise (1: the status is set
 //                                  to relocalisation before the last frame), n_cells, the map's cell order, then
-//                                  optionally d0 .. d4 (the lens; the frames are then raw images);
-//                                  IMAGES.raw: the frames, W x H bytes each; prints per frame "frame k result status
+//                                  optionally d0 .. d4 (the lens; the frames are then raw images), then optionally
+//                                  pixel_format (SVO_PIXEL_*) and gray16_shift (absent: 8-bit grey frames);
+//                                  IMAGES.raw: the frames, packed, W x H pixels of that format each; prints per frame "frame k result status
 //                                  keyframe n_obs n_obs_points seeds candidates keyframes", "pose" + the cur pose[7]
 //                                  with %a, "removed" + frame:index of the features the BA removed (frame ids
 //                                  relative to the first), "time" + step=seconds, and last the trajectory lines; an
@@ -511,14 +512,24 @@ int main(int argc, char** argv) {
             const int nFrames = (int)d[19];
             const bool relocalise = d[20] != 0.0;
             const size_t nCells = (size_t)d[21];
-            if (nd != 22 + nCells && nd != 27 + nCells) throw std::runtime_error("system: DATA.bin size mismatch");
-            if (nd == 27 + nCells) {
+            // the optional tail: d0..d4 (5 values), then pixel_format and gray16_shift (2 values), either or both
+            const size_t tail = nd - 22 < nCells ? 1 : nd - 22 - nCells;
+            if (tail != 0 && tail != 2 && tail != 5 && tail != 7) throw std::runtime_error("system: DATA.bin size mismatch");
+            if (tail >= 5) {
                 const double* l = d + 22 + nCells;
                 c.m_d0 = l[0]; c.m_d1 = l[1]; c.m_d2 = l[2]; c.m_d3 = l[3]; c.m_d4 = l[4];
             }
+            if (tail == 2 || tail == 7) {
+                c.m_pixelFormat = (int32_t)d[nd - 2];
+                c.m_gray16Shift = (int32_t)d[nd - 1];
+            }
+            const svo_image_layout packed{c.m_pixelFormat, c.m_gray16Shift, 0, 0};
+            int64_t layoutBytes = 0;  // of one packed frame in the Config's pixel format
+            if (svo_image_layout_bytes(&packed, c.m_imgWidth, c.m_imgHeight, 1, &layoutBytes) != SVO_OK)
+                throw std::runtime_error(std::string("system: ") + svo_last_error());
             std::vector<int32_t> order(nCells);
             for (size_t i = 0; i < nCells; ++i) order[i] = (int32_t)d[22 + i];
-            const size_t frameBytes = (size_t)c.m_imgWidth * c.m_imgHeight;
+            const size_t frameBytes = (size_t)layoutBytes;
             const std::vector<uint8_t> imgs = read_raw(argv[3], frameBytes * (size_t)nFrames);
             const int passes = argc > 4 ? std::atoi(argv[4]) : 1;
             Context ctx(0);

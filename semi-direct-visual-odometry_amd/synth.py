@@ -294,7 +294,8 @@ def write_map_problem(p, directory, cell_order):
 def write_system_problem(config, images, cell_order, directory, relocalise=False):
     """Files for build/svo_host_check system (the C++ mirror's System): system.bin (doubles, layout in
     host/svo_host_check.cpp: the Config fields, the number of frames, the relocalise flag, the map's cell order, and
-    d0..d4 when one of them is non-zero) and images.raw (the frames).  Returns the two paths."""
+    d0..d4 when one of them is non-zero, and pixel_format, gray16_shift when the format is not gray8) and images.raw (the
+    frames, packed, in the Config's pixel format).  Returns the two paths."""
     import os
     c = config
     hdr = [c.fx, c.fy, c.cx, c.cy, c.img_width, c.img_height, c.cell_pixel_size,
@@ -304,7 +305,10 @@ def write_system_problem(config, images, cell_order, directory, relocalise=False
            c.threshold_gradient_magnitude, c.median_mode, len(images), int(relocalise), len(cell_order)]
     data, raw = os.path.join(str(directory), "system.bin"), os.path.join(str(directory), "images.raw")
     d = [getattr(c, "d%d" % i, 0.0) for i in range(5)]
+    from ._capi import PIXEL_FORMATS, PIXEL_SHAPES
+    pixel_format = getattr(c, "pixel_format", "gray8")
+    fmt = [PIXEL_FORMATS[pixel_format], getattr(c, "gray16_shift", 8)] if pixel_format != "gray8" else []
     np.concatenate([np.array(hdr, np.float64), np.asarray(cell_order, np.float64),
-                    np.array(d if any(d) else [], np.float64)]).tofile(data)
-    np.ascontiguousarray(images, np.uint8).tofile(raw)
+                    np.array(d if any(d) else [], np.float64), np.array(fmt, np.float64)]).tofile(data)
+    np.ascontiguousarray(images, PIXEL_SHAPES[pixel_format][1]).tofile(raw)
     return data, raw

@@ -16,7 +16,10 @@ every key once per mirror ("python", "cpp").
 With --lens k1,k2,p1,p2,k3 the camera has that lens: the frames are made raw on the host first (tests/undistort_ref.py
 distort_image) and the System undistorts them on the device, so "frame" then includes the remap.
 
-    python tools/system_time.py [--frames 32] [--reps 3] [--lens k1,k2,p1,p2,k3]
+With --pixel-format rgb8 (or bgr8, rgba8, bgra8) every frame is handed over as colour with R = G = B = the grey frame,
+so the conversion on the device gives the same grey image and the same run, and "frame" then includes the conversion.
+
+    python tools/system_time.py [--frames 32] [--reps 3] [--lens k1,k2,p1,p2,k3] [--pixel-format rgb8]
 """
 import argparse
 import json
@@ -94,6 +97,7 @@ def main():
     ap.add_argument("--frames", type=int, default=32)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--lens", default="")
+    ap.add_argument("--pixel-format", default="gray8", choices=("gray8", "bgr8", "rgb8", "bgra8", "rgba8"))
     a = ap.parse_args()
     images, _ = SC.make_sequence(a.frames, W, H)
     cfg = svo_amd.Config(desired_detected_points_for_initialization=1000)  # SSC keeps about half: ~500 of 546 cells
@@ -105,6 +109,11 @@ def main():
         images = np.stack([U.distort_image(img, cam, lens) for img in images])
         for k, v in enumerate(lens):
             setattr(cfg, "d%d" % k, v)
+    if a.pixel_format != "gray8":
+        import numpy as np
+        from svo_amd._capi import PIXEL_SHAPES
+        images = np.stack([images] * PIXEL_SHAPES[a.pixel_format][2], axis=-1)
+        cfg.pixel_format = a.pixel_format
     one_pass(images, cfg)  # warm-up
     rows = []
     for _ in range(a.reps):
@@ -113,6 +122,7 @@ def main():
     S = svo_amd.System
     cpp = [r for p in cpp_passes(images, cfg, system.map.cell_orders, a.reps + 1)[1:] for r in p[2:]]
     out = {"tool": "system_time", "width": W, "height": H, "frames": a.frames, "reps": a.reps, "lens": lens,
+           "pixel_format": a.pixel_format,
            "keyframes_in_map": system.map.size_keyframes(), "seeds": system.depth_estimator.number_filters(),
            "python": summarise(rows, S), "cpp": summarise(cpp, S)}
     print(json.dumps(out))

@@ -230,7 +230,9 @@ int svo_robust_scale_capacity(int32_t impl, int64_t* slots);
  * LM step, pixelPos <- flow.xy.  Candidate i's reference feature lives in frame ref_frames[i]
  * (refFeature->m_frame; NULL = every candidate in ref_frame) at ref_px[i] (its m_pixelPosition).
  * px_inout: n x 2 (initial pixel positions in, aligned out); err: the returned RMSE (NaN when the
- * patch left the frame); status: Optimizer::Status.  Synchronous. */
+ * patch left the frame); status: Optimizer::Status.  patch_size: footprint (2 (patch_size / 2) + 1)^2 <= 128 px
+ * (patch_size <= 11); with patch_size 1 (one observation, three unknowns) nothing moves: status Non_Suff_Points,
+ * err -1 (src/optimizer.cpp:53-54).  Synchronous. */
 int svo_feature_align(svo_ctx* ctx, const svo_camera* cam, int32_t patch_size, const svo_pyramid_set* ref_set,
                       const int32_t* ref_frames, int32_t ref_frame, const svo_pyramid_set* cur_set, int32_t cur_frame,
                       int32_t n, const double* ref_px, double* px_inout, double* err, int32_t* status);

@@ -154,7 +154,12 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) feature_align_kernel(Feat
     double sums[13];
 #pragma unroll
     for (int t = 0; t < 13; ++t) sums[t] = __shfl(acc, t, 64);
-    if (active && lane == 0) {
+    if (active && lane == 0 && A < 3) {
+        // fewer observations than unknowns (patch 1): optimizeLM returns (Non_Suff_Points, -1) before its first
+        // step (src/optimizer.cpp:53-54) and the pixel stays where it was
+        a.err[i] = -1.0;
+        a.status[i] = kNonSuffPoints;
+    } else if (active && lane == 0) {
         double Hm[9], g[3];
         for (int t = 0; t < 9; ++t) Hm[t] = sums[t];
         for (int t = 0; t < 3; ++t) g[t] = sums[9 + t];

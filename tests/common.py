@@ -1,4 +1,6 @@
-"""Shared helpers for the parity tests: synthetic pairs, oracle runs, GPU batches."""
+"""Shared helpers for the parity tests: synthetic pairs, oracle runs, GPU batches, per-level trace checks."""
+import dataclasses
+
 import numpy as np
 
 import oracle as O
@@ -19,6 +21,14 @@ def canon(p):
 
 def make_pairs(n, seed0=synth.SEED_BASE, **kw):
     return [synth.make_pair(seed=seed0 + i, **kw) for i in range(n)]
+
+
+def take(s, n_ref, n_kf):
+    """A copy of pair `s` with its first n_ref ref features and its first n_kf kf features."""
+    assert 0 <= n_ref <= s.n_ref and 0 <= n_kf <= s.n_kf, (n_ref, s.n_ref, n_kf, s.n_kf)
+    idx = np.concatenate([np.arange(n_ref), s.n_ref + np.arange(n_kf)]).astype(np.int64)
+    return dataclasses.replace(s, n_ref=int(n_ref), n_kf=int(n_kf), px=s.px[idx].copy(), bearing=s.bearing[idx].copy(),
+                               point=s.point[idx].copy(), has_point=s.has_point[idx].copy())
 
 
 def oracle_pyramids(s, levels):
@@ -47,3 +57,31 @@ def gpu_batch(pairs, patch, min_level, max_level, ctx=None, max_features=None, m
         b.set_pair(i, (ps, 3 * i), (ps, 3 * i + 1), (ps, 3 * i + 2), s.ref_pose, s.kf_pose, s.cur_init_pose,
                    s.n_ref, s.n_kf, s.px, s.bearing, s.point, s.has_point)
     return b, ps
+
+
+def check_traces(tr_gpu, tr_cpu, min_level, max_level, exact_levels):
+    """Per-level traces of an exact-mode alignment against the oracle's (median_mode 1): DESIGN.md §2."""
+    for l in range(max_level, min_level - 1, -1):
+        g, c = tr_gpu[l], tr_cpu[l]
+        assert (g.n_ref_vis, g.n_vis, g.status) == (c.n_ref_vis, c.n_vis, c.status), (l, g.n_vis, c.n_vis)
+        if l in exact_levels:
+            assert g.median == c.median and g.mad == c.mad and g.sigma == c.sigma, l
+        else:
+            assert abs(g.sigma - c.sigma) <= 1e-9 * abs(c.sigma), l
+        Hg = np.tril(np.array(g.H).reshape(6, 6))
+        Hc = np.tril(np.array(c.H).reshape(6, 6))
+        assert np.abs(Hg - Hc).max() <= 1e-10 * np.abs(Hc).max(), l
+        gg, gc = np.array(g.g), np.array(c.g)
+        assert np.abs(gg - gc).max() <= 1e-9 * max(np.abs(gc).max(), 1e-300), l
+        assert abs(g.chi2 - c.chi2) <= 1e-10 * c.chi2, l
+
+
+def check_ref_traces(tr_gpu, tr_cpu, min_level, max_level):
+    """Per-level traces of a reference-mode alignment against the oracle's std::nth_element path (median_mode 0)."""
+    for l in range(max_level, min_level - 1, -1):
+        g, c = tr_gpu[l], tr_cpu[l]
+        assert (g.n_ref_vis, g.n_vis, g.status) == (c.n_ref_vis, c.n_vis, c.status), (l, g.n_vis, c.n_vis)
+        if l == max_level:  # later levels start from poses that differ by ~1e-13 (summation order)
+            assert (g.median, g.mad, g.sigma) == (c.median, c.mad, c.sigma), (l, g.median, c.median, g.mad, c.mad)
+        else:
+            assert abs(g.sigma - c.sigma) <= 1e-9 * abs(c.sigma), l

@@ -17,8 +17,8 @@ import pytest
 import oracle as O
 import svo_amd
 import svo_amd.synth as synth
-from common import canon, gpu_batch, make_pairs, oracle_align
-from svo_amd._capi import check, lib
+from common import canon, check_traces as _check_traces, gpu_batch, make_pairs, oracle_align
+from svo_amd._capi import SVO_ERR_ARG, check, lib
 
 pytestmark = pytest.mark.gpu
 
@@ -49,22 +49,6 @@ def test_pyramid_bitexact():
             for l in range(lv):
                 assert np.array_equal(ps.download(i, l, False), li[l]), (h, w, i, l, "image")
                 assert np.array_equal(ps.download(i, l, True), lg[l]), (h, w, i, l, "gradient")
-
-
-def _check_traces(tr_gpu, tr_cpu, min_level, max_level, exact_levels):
-    for l in range(max_level, min_level - 1, -1):
-        g, c = tr_gpu[l], tr_cpu[l]
-        assert (g.n_ref_vis, g.n_vis, g.status) == (c.n_ref_vis, c.n_vis, c.status), (l, g.n_vis, c.n_vis)
-        if l in exact_levels:
-            assert g.median == c.median and g.mad == c.mad and g.sigma == c.sigma, l
-        else:
-            assert abs(g.sigma - c.sigma) <= 1e-9 * abs(c.sigma), l
-        Hg = np.tril(np.array(g.H).reshape(6, 6))
-        Hc = np.tril(np.array(c.H).reshape(6, 6))
-        assert np.abs(Hg - Hc).max() <= 1e-10 * np.abs(Hc).max(), l
-        gg, gc = np.array(g.g), np.array(c.g)
-        assert np.abs(gg - gc).max() <= 1e-9 * max(np.abs(gc).max(), 1e-300), l
-        assert abs(g.chi2 - c.chi2) <= 1e-10 * c.chi2, l
 
 
 @pytest.mark.parametrize("cfg", [dict(patch=5, min_level=0, max_level=4, nf=2000),   # config 2
@@ -225,28 +209,51 @@ def test_class_surface_align():
     assert ref.image_pyramid.get_image_size_at_level(5) == (0, 0)
 
 
-@pytest.mark.parametrize("patch", [7, 8, 5])
+# patch 7, 8, 5: the KITTI frame and 2000 candidates; the other footprints (1, 9 and 121 px; patch 9 shares half 4 with
+# patch 8) on a 320 x 240 pair with 300 candidates.  The area is a run-time argument of the kernel, up to 128 px.
+@pytest.mark.parametrize("patch", [7, 8, 5, 1, 2, 3, 9, 11])
 def test_feature_align_bitexact(patch):
-    s = synth.make_pair(n_features=2000, patch_size=patch)
+    small = patch not in (7, 8, 5)
+    W, H, n = (320, 240, 300) if small else (1241, 376, 2000)
+    s = synth.make_pair(n_features=n, patch_size=patch, width=W, height=H)
     rng = np.random.default_rng(patch)
     ref_grad = O.build_pyramid(s.ref_img, 1)[1]
     cur_grad = O.build_pyramid(s.cur_img, 1)[1]
-    n = 2000
     ref_px = s.px[:n].copy()
     init = ref_px + rng.uniform(-1.5, 1.5, ref_px.shape)
-    init[:5] = [[-3, 10], [2, 2], [1240.5, 100], [600, 375.9], [3.5, 3.5]]  # out-of-frame / border cases
+    # out-of-frame / border cases
+    init[:5] = [[-3, 10], [2, 2], [319.5, 100], [155, 239.9], [3.5, 3.5]] if small else \
+        [[-3, 10], [2, 2], [1240.5, 100], [600, 375.9], [3.5, 3.5]]
     px_c, err_c, st_c = O.feature_align(s.camera, patch, ref_grad, cur_grad, ref_px, init)
-    ps = svo_amd.PyramidSet(2, 1241, 376, 1)
+    ps = svo_amd.PyramidSet(2, W, H, 1)
     ps.upload(0, np.stack([s.ref_img, s.cur_img]))
     ps.build()
     px_g = init.copy()
     fa = svo_amd.FeatureAlignment(patch)
-    err_g, st_g = fa.align_batch(ps, 0, ps, 1, ref_px, px_g, svo_amd.PinholeCamera.kitti())
+    cam = s.camera
+    camera = svo_amd.PinholeCamera(cam["width"], cam["height"], cam["fx"], cam["fy"], cam["cx"], cam["cy"])
+    err_g, st_g = fa.align_batch(ps, 0, ps, 1, ref_px, px_g, camera)
     assert np.array_equal(px_g, px_c)
     assert np.array_equal(st_g, st_c)
     assert np.array_equal(np.isnan(err_g), np.isnan(err_c))
     ok = ~np.isnan(err_c)
     assert np.array_equal(err_g[ok], err_c[ok])
+
+
+def test_feature_align_rejects_a_footprint_past_128_px():
+    """Patch 12 (half 6, 169 px) does not fit the kernel's per-wave LDS rows: SVO_ERR_ARG, nothing launched."""
+    s = synth.make_pair(n_features=8, patch_size=12, width=320, height=240)
+    cam = s.camera
+    camera = svo_amd.PinholeCamera(cam["width"], cam["height"], cam["fx"], cam["fy"], cam["cx"], cam["cy"])
+    ps = svo_amd.PyramidSet(2, 320, 240, 1)
+    ps.upload(0, np.stack([s.ref_img, s.cur_img]))
+    ps.build()
+    px = np.ascontiguousarray(s.px[:8] + 0.5)
+    before = px.copy()
+    with pytest.raises(svo_amd.SvoError) as e:
+        svo_amd.FeatureAlignment(12).align_batch(ps, 0, ps, 1, s.px[:8], px, camera)
+    assert e.value.code == SVO_ERR_ARG and np.array_equal(px, before)
+    svo_amd.FeatureAlignment(11).align_batch(ps, 0, ps, 1, s.px[:8], px, camera)  # 121 px: the largest footprint
 
 
 def test_feature_align_large_batch_pageable_staging():

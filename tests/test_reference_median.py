@@ -23,7 +23,7 @@ import pytest
 import oracle as O
 import svo_amd
 import svo_amd.synth as synth
-from common import canon, gpu_batch, make_pairs, oracle_align
+from common import canon, check_ref_traces as _check_ref_traces, gpu_batch, make_pairs, oracle_align
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DBL_MAX = np.finfo(np.float64).max
@@ -151,16 +151,6 @@ def test_debug_robust_scale_heap_select_path(tmp_path):
         for impl in (svo_amd.SCALE_K2V, svo_amd.SCALE_K2R):
             med, mad = svo_amd.debug_robust_scale(v, len(v), impl=impl)
             assert med == med_c and mad == mad_c, (n, impl, med, med_c, mad, mad_c)
-
-
-def _check_ref_traces(tr_gpu, tr_cpu, min_level, max_level):
-    for l in range(max_level, min_level - 1, -1):
-        g, c = tr_gpu[l], tr_cpu[l]
-        assert (g.n_ref_vis, g.n_vis, g.status) == (c.n_ref_vis, c.n_vis, c.status), (l, g.n_vis, c.n_vis)
-        if l == max_level:  # later levels start from poses that differ by ~1e-13 (summation order)
-            assert (g.median, g.mad, g.sigma) == (c.median, c.mad, c.sigma), (l, g.median, c.median, g.mad, c.mad)
-        else:
-            assert abs(g.sigma - c.sigma) <= 1e-9 * abs(c.sigma), l
 
 
 @pytest.mark.gpu
